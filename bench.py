@@ -2,6 +2,7 @@
 """bench.py -- WaveFormer encoder forward on MI355X (BASELINE.json configs[1]).
 
     python bench.py [--gpus N --steps K --warmup W --batch B --precision bf16x3|bf16|fp16]
+                    [--dump-outputs DIR] [--full]
     python bench.py --workload full --img 192 --precision fp16    (config 5)
 
 One step = one MultiscaleTransformer forward (PatchEmbed -> 4 stages of DWT / window
@@ -11,7 +12,11 @@ waveformer_amd HIP kernels.  N > 1 (launched by torch.distributed.run, one proce
 runs N independent replicas -- 128^3 crops do not shard -- and reports the
 whole-job rate: B * K * N volumes / the slowest rank's wall time.
 
-Rank 0 prints ONE JSON line.  Besides the driver contract it carries:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps (ms_per_step =
+the timed region / K) and prints the line.  --dump-outputs DIR also writes what the last timed
+step returned (rank 0's; for the encoder its 4 stage outputs and their detail bands) as
+DIR/<name>.npy, float32, at most 64 MB in all; inputs and weights are seeded, so two builds
+run with the same arguments are comparable array for array.  With --full the line also carries:
   roofline     : the dominant kernel of the step (the CCF_FFN depthwise conv): its algorithmic
                  bytes per launch / its average launch duration, timed with HIP events on the
                  launch stream (eager repeats of the step after the timed region), against the
@@ -71,12 +76,21 @@ def parse():
                     help="volumes per GPU per step (default: 8 for encoder, 1 for train)")
     ap.add_argument("--precision", default="bf16x3", choices=["bf16x3", "bf16", "fp16"])
     ap.add_argument("--graph", type=int, default=1, help="replay the step as a HIP graph")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not "
+                         "need: the per-op rooflines, the Dice parity against the reference's "
+                         "labels and the CPU baseline (each can be switched off below).  Without "
+                         "it the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float32; "
+                         "rank 0's; at most 64 MB in all -- a fixed seeded sample of the elements "
+                         "of larger outputs)")
     ap.add_argument("--roofline-op", default="auto")
-    ap.add_argument("--cpu-baseline", type=int, default=1)
-    ap.add_argument("--parity", type=int, default=1)
+    ap.add_argument("--cpu-baseline", type=int, default=1, help="with --full: 0 skips it")
+    ap.add_argument("--parity", type=int, default=1, help="with --full: 0 skips it")
     ap.add_argument("--op-timers", type=int, default=1,
-                    help="0: skip the per-op roofline timing after the timed region (a rocprof "
-                         "trace then holds the warm-up and the graph replays only)")
+                    help="with --full: 0 skips the per-op roofline timing after the timed region "
+                         "(a rocprof trace then holds the warm-up and the graph replays only)")
     ap.add_argument("--img", type=int, default=128)
     ap.add_argument("--workload", default="encoder",
                     choices=["encoder", "full", "sliding", "train"],
@@ -103,7 +117,58 @@ def parse():
         args.steps = {"encoder": 250, "full": 40}.get(args.workload, 20)
     if args.warmup is None:
         args.warmup = 10 if args.workload == "encoder" else 3
+    if not args.full:  # a plain run: only what the headline figure needs
+        args.cpu_baseline = args.parity = args.op_timers = 0
     return args
+
+
+# ------------------------------------------------------------------------------------------
+# --dump-outputs: the arrays the timed path returned in its last step
+# ------------------------------------------------------------------------------------------
+DUMP_BUDGET_BYTES = 60 * 10 ** 6  # of array data: with the .npy headers well within 64 MB
+DUMP_SEED = 20240607
+
+
+def named_outputs(out, prefix="out"):
+    """Flatten what a step returned (a tensor, or tuples / lists / dicts of them) into
+    [(name, tensor)] with names that spell the path: out0, hf1_0_aad, ...  The encoder's
+    (outs, hfs) pair becomes out<stage> and hf<stage>_<level>_<band>."""
+    if torch.is_tensor(out):
+        return [(prefix, out)]
+    res = []
+    if isinstance(out, dict):
+        for k in sorted(out):
+            res += named_outputs(out[k], f"{prefix}_{k}")
+    elif isinstance(out, (tuple, list)):
+        for i, v in enumerate(out):
+            res += named_outputs(v, f"{prefix}{i}" if prefix[-1:].isalpha() else f"{prefix}_{i}")
+    return res  # None and other non-tensor leaves carry no array
+
+
+def dump_outputs(dirname, out):
+    """Write every tensor of `out` as <dirname>/<name>.npy in float32.  All of them together stay
+    under DUMP_BUDGET_BYTES: the budget is split evenly over the tensors, a tensor within its
+    share is written whole (its own shape), a larger one as the 1-D array of its elements at
+    share / 4 flat indices drawn once from a CPU generator seeded with DUMP_SEED and the
+    tensor's position and size -- the same indices for the same arguments, whatever build."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    if isinstance(out, tuple) and len(out) == 2 and isinstance(out[0], (tuple, list)):
+        items = named_outputs(out[0], "out") + named_outputs(out[1], "hf")  # encoder (outs, hfs)
+    else:
+        items = named_outputs(out, "out")
+    share = DUMP_BUDGET_BYTES // max(1, len(items)) // 4  # float32 elements per tensor
+    written = {}
+    for pos, (name, t) in enumerate(items):
+        t = t.detach()
+        if t.numel() > share:
+            g = torch.Generator().manual_seed(DUMP_SEED + 1000003 * pos + t.numel() % 1000003)
+            idx = torch.randint(0, t.numel(), (share,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.float().cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
 
 
 # ------------------------------------------------------------------------------------------
@@ -433,7 +498,7 @@ def main_sliding(args, world, rank, dev):
                 return inferers.maybe_mirror_and_predict(x, model, inf, axes)
             return inf(x, model)
 
-    stitch = OpTimer("sliding_window_stitch")
+    stitch = OpTimer("sliding_window_stitch") if args.full else None
     for _ in range(max(1, args.warmup)):
         y = step()
     torch.cuda.synchronize()
@@ -450,12 +515,16 @@ def main_sliding(args, world, rank, dev):
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
-    conv = OpTimer("conv3d_k3")
-    stitch.active = conv.active = True
-    step()
-    stitch.active = conv.active = False
-    r = stitch.summary()
-    rc = conv.summary()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, y)
+    r = rc = None
+    if args.full:  # per-kernel rooflines: one more, eager, step with the op timers on
+        conv = OpTimer("conv3d_k3")
+        stitch.active = conv.active = True
+        step()
+        stitch.active = conv.active = False
+        r = stitch.summary()
+        rc = conv.summary()
     if rank == 0:
         nwin = 18 * (8 if axes else 1)
         out = {
@@ -568,6 +637,8 @@ def main_train(args, world, rank, dev):
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": last})
     if rank == 0:
         vols = args.batch * args.steps * world
         out = {
@@ -673,9 +744,11 @@ def main():
                     generator=torch.Generator(device=dev).manual_seed(1234 + rank))
 
     roof_op = args.roofline_op if args.roofline_op != "auto" else "ccf_ffn_dwconv"
-    timers = {n: OpTimer(n) for n in dict.fromkeys(
-        [roof_op, "dwt3d_haar", "dwt3d_haar_ll", "msfuse", "window_attention"]
-        + (["conv3d_k3"] if full else []))}
+    timers = {}
+    if args.op_timers:
+        timers = {n: OpTimer(n) for n in dict.fromkeys(
+            [roof_op, "dwt3d_haar", "dwt3d_haar_ll", "msfuse", "window_attention"]
+            + (["conv3d_k3"] if full else []))}
 
     def step():
         with torch.no_grad():
@@ -686,6 +759,7 @@ def main():
     torch.cuda.synchronize()
 
     graph = None
+    last = None  # what the last timed step returned (a replayed graph's static outputs)
     if args.graph:
         try:
             s = torch.cuda.Stream()
@@ -696,19 +770,20 @@ def main():
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                step()
+                last = step()
             graph.replay()
             torch.cuda.synchronize()
         except Exception as e:  # capture unsupported -> eager, said in the output
-            graph = None
+            graph = last = None
             print(f"[bench] graph capture failed ({e}); timing eager launches", file=sys.stderr)
 
     def run_steps(k):
+        nonlocal last
         for _ in range(k):
             if graph is not None:
                 graph.replay()
             else:
-                step()
+                last = step()
 
     if world > 1:
         dist.barrier()
@@ -722,6 +797,9 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, last)
 
     # per-launch roofline timing of the dominant streaming kernel (eager launches, so the HIP
     # events sit on the launch stream around each launch)
@@ -763,6 +841,8 @@ def main():
                        "parallelism": f"replicas x{world} (no data-path collective)",
                        "hip_graph": graph is not None},
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped  # name -> shape of DIR/<name>.npy
         def roofline(name, r):
             if name in ("window_attention", "conv3d_k3"):
                 # MFMA-bound: algorithmic FLOPs vs the dense bf16 / fp16 peak (the same 2.5

@@ -1,6 +1,8 @@
 """bench.py's own rank launcher (CPU): `python bench.py --gpus N` with no WORLD_SIZE starts N
 ranks through torch.distributed.run (light_training/launch.py:81-112 re-launches the same way);
-as a rank, or with N = 1, it does not relaunch."""
+as a rank, or with N = 1, it does not relaunch.  Also its host-side options: a plain run
+switches the roofline / parity / CPU-baseline legs off (--full brings them back), and
+--dump-outputs writes float32 arrays within its byte budget, sampled at fixed indices."""
 import os
 import sys
 from types import SimpleNamespace
@@ -37,6 +39,39 @@ def test_relaunch_runs_child(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8"])
     assert bench.maybe_launch_ranks(SimpleNamespace(gpus=8)) == 3
     assert "--nproc-per-node=8" in seen["cmd"] and seen["cmd"][-2:] == ["--gpus", "8"]
+
+
+def test_plain_run_switches_the_extra_legs_off(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert (a.op_timers, a.parity, a.cpu_baseline) == (0, 0, 0)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--parity", "0"])
+    a = bench.parse()
+    assert a.full and (a.op_timers, a.parity, a.cpu_baseline) == (1, 0, 1)
+
+
+def test_dump_outputs_names_budget_and_fixed_sample(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * 4 * 100)  # 4 arrays x 100 floats
+    big = torch.arange(1000, dtype=torch.float64).reshape(10, 100).t()  # non-contiguous view
+    outs = [torch.ones(2, 3), big]
+    hfs = [[{"aad": torch.zeros(5), "ada": torch.full((7,), 2.0).half()}], []]
+    for d in ("a", "b"):
+        shapes = bench.dump_outputs(str(tmp_path / d), (outs, hfs))
+    assert shapes == {"out0": [2, 3], "out1": [100], "hf0_0_aad": [5], "hf0_0_ada": [7]}
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in shapes}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= 4 * 4 * 100
+    assert np.array_equal(got["out0"], np.ones((2, 3))) and np.array_equal(got["hf0_0_ada"],
+                                                                          np.full(7, 2.0))
+    # the sample: elements of the logical (row-major) order, the same ones in every run
+    flat = big.reshape(-1).numpy()
+    assert np.isin(got["out1"], flat).all() and len(np.unique(got["out1"])) > 50
+    assert np.array_equal(got["out1"], np.load(tmp_path / "b" / "out1.npy"))
+    # a bare tensor (the full model's logits) is one array named "out"
+    assert bench.dump_outputs(str(tmp_path / "c"), torch.ones(3)) == {"out": [3]}
 
 
 def test_stamp_marks_rehearsal(monkeypatch):
