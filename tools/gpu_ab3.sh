@@ -1,6 +1,6 @@
 #!/bin/bash
 # Interleaved A/B (3 rounds) of stage-1 FFN back-half variants at B = 8 under a kernel trace.
-# Each argument is LIB[:ENV=VAL]; e.g. abso/libwf_pk.so abso/libwf_pk.so:WF_FFN_DWFC_WS=1
+# Each argument is LIB[:ENV=VAL]; e.g. abso/libwf_pk.so abso/libwf_pk.so:WF_FFN_NO_DWFC=1
 set -o pipefail
 TAG=$1; shift
 export TMPDIR=/tmp

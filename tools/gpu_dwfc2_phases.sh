@@ -1,6 +1,7 @@
 #!/bin/bash
 # ffn_dwfc2 phase attribution: the B = 8 stage-2 FFN with phases of the fused kernel skipped
 # (WF_FFN_DBG bits: 1 scatter, 2 LN2, 4 fc, 8 fetch/commit; results invalid), kernel trace.
+# Needs a library built with `make EXTRA=-DWF_FFN_DBG=1`; the default library ignores the variable.
 set -o pipefail
 TAG=${1:-dwfc2ph}
 OUT=gpurun_out/$TAG

@@ -1,5 +1,5 @@
 """conv3d_k3 timing at the config-3 / config-5 decoder shapes under the environment's switches
-(WF_CONV_PERSIST, WF_CONV_RW, ...), HIP events around ITERS calls per shape:
+(WF_CONV_WIDE, ...), HIP events around ITERS calls per shape:
     python tools/kbench_conv_ab.py            (one line per shape)"""
 import os
 import sys

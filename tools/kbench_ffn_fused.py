@@ -1,6 +1,7 @@
 """Phase attribution of the whole-FFN kernel (ffn_fused.hip): the stage-1 CCF_FFN op at
 B x 64^3 x 48 timed with HIP events for each WF_FFN_DBG phase mask (results of a masked build
-are invalid -- only the time counts).  Usage: python tools/kbench_ffn_fused.py [masks...]"""
+are invalid -- only the time counts).  Needs a library built with `make EXTRA=-DWF_FFN_DBG=1`
+(WAVEFORMER_HIP_LIB); the default library ignores the variable.  Usage: python tools/kbench_ffn_fused.py [masks...]"""
 import os
 import sys
 

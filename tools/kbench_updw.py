@@ -1,6 +1,6 @@
 """Fused up-sample + depthwise conv (ProjectionUpsample.conv1) vs the two-kernel path at the
 config-5 shapes (img 192, B 2: learnable_up4 192 ch 24^3 -> 96^3, learnable_up3 96 ch 48^3 ->
-96^3), HIP-event timed (developer tool).  Env WF_UPDW_PF picks the fused kernel variant."""
+96^3), HIP-event timed (developer tool)."""
 import torch
 from waveformer_amd import ops, _lib
 

@@ -6,9 +6,9 @@ forward kernel (saving what its backward needs) and whose backward is the HIP ba
 of csrc/train.hip.  The dense GEMMs of the step run on the library's own MFMA GEMMs at bf16x3
 (fp32-faithful operands, fp32 accumulation): the data gradients dX = dY W and the 1x1 /
 transposed-conv forwards on the streaming GEMM (ops.mm_rows / linear_rows_any /
-convtranspose2_cl), the weight gradients dW = dY^T X on wf_gemm_tn -- no hipBLASLt on the
-step, except the shapes those kernels do not take (a channel count not a multiple of 8 / 4:
-the 4-channel input and output convolutions), which fall back to torch.mm.  The modules in
+convtranspose2_cl), the weight gradients dW = dY^T X on wf_gemm_tn -- no hipBLASLt kernel
+runs in the step: the 4-channel input and output convolutions (K < 8) take the small-K kernel
+(wf_linear_smallk_fwd, exact fp32 FMAs).  The modules in
 network_models switch to these Functions when autograd is recording (`needs_grad`);
 inference keeps the fused kernels.
 
@@ -18,7 +18,6 @@ workspaces the backward consumes are fp32 in that mode.
 from __future__ import annotations
 
 import ctypes
-import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -294,9 +293,6 @@ def _rows(x: torch.Tensor) -> torch.Tensor:
     return ops.to_cl(x).permute(0, 2, 3, 4, 1)
 
 
-_TORCH_CONV = os.environ.get("WF_TRAIN_TORCH_CONV") == "1"
-
-
 def conv_train(conv: torch.nn.Module, x: torch.Tensor) -> torch.Tensor:
     """A decoder Conv3d / ConvTranspose3d on the waveformer_amd paths (autograd-aware):
     3^3 dense (Conv3dK3), 3^3 depthwise (DWConv3dK3), 1^3 (F.linear over channel-last rows),
@@ -304,10 +300,6 @@ def conv_train(conv: torch.nn.Module, x: torch.Tensor) -> torch.Tensor:
     F = torch.nn.functional
     nn = torch.nn
     ok = x.is_cuda and x.dtype == torch.float32 and x.dim() == 5
-    if _TORCH_CONV and type(conv) is nn.Conv3d and conv.kernel_size == (3, 3, 3):
-        # diagnostics only (tools/grad128_diag.py): the 3^3 convs on the framework's fp32
-        # convolution, to attribute the gradient error of the bf16x3 kernels
-        return conv(x.contiguous())
     if ok and type(conv) is nn.Conv3d and conv.padding_mode == "zeros" \
             and conv.dilation == (1, 1, 1) and conv.stride == (1, 1, 1):
         Cin, Cout = conv.in_channels, conv.out_channels

@@ -8,7 +8,8 @@ These are the decoder's full-resolution 3^3 convolutions.  In
 (ops.instnorm_stats / ops.norm_act), the 1x1 residual conv as one GEMM.  Training (autograd)
 runs every convolution through wfa.conv_train: the 3^3 convs on the HIP forward / input- /
 weight-gradient kernels, 1x1 and 2^3 transposed convs on the library's MFMA GEMMs -- no MIOpen
-convolution, hence no MIOpen find, and no hipBLASLt but for the 4-channel shapes.  norm_name is always "instance" (InstanceNorm3d, affine=False) and the
+convolution, hence no MIOpen find, and no hipBLASLt kernel (the 4-channel shapes take the
+small-K kernel).  norm_name is always "instance" (InstanceNorm3d, affine=False) and the
 activation LeakyReLU(0.01), as Waveformer builds them.
 """
 from __future__ import annotations

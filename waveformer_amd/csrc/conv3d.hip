@@ -57,7 +57,6 @@ struct Conv3Args {
   float* part;        // (ksplit, B*D*H*W, Cout) split-K partials (ksplit > 1)
   double* stats;      // (B, Cout, 2) fp64 {sum, sum of squares} accumulator or nullptr: the
                       // InstanceNorm statistics of the output, fused into the epilogue
-  int zfirst;         // tile order: z fastest (1) or x fastest (0)
   const uint16_t* xh; // XH kernels: the input as fp16 (the operands WF_PREC_FP16 stages; same
                       // positions / ldx as x)
   int dbg;            // WF_CONV_DBG builds: 1 no activation loads, 2 no activation LDS stores,
@@ -70,7 +69,7 @@ struct Conv3Args {
 // XH: the input is already fp16 in HBM (written by the producing norm_act with the same
 // round-to-nearest-even conversion this kernel's fp16 staging applies, so the operands are
 // bitwise those of the fp32 input): half the staging bytes, no convert
-template <int CO_T, int NT, int P, bool PIPE = false, int RW = 1, bool XH = false>
+template <int CO_T, int NT, int P, int RW = 1, bool XH = false>
 __global__ __launch_bounds__(256, 2) void conv3d_k3_kernel(Conv3Args a) {
   constexpr bool SPLIT = P == PREC_SPLIT;  // P: Prec (operand kind)
   static_assert(!XH || P == PREC_FP16, "fp16 input only with fp16 operands");
@@ -95,25 +94,15 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_kernel(Conv3Args a) {
   // XCDs; give each XCD a contiguous run of tiles so z / y neighbours share its L2
   int64_t t = blockIdx.x;
   if ((a.nblocks & 7) == 0) t = (t & 7) * (a.nblocks >> 3) + (t >> 3);
-  int tx, ty, z, b;
-  if (a.zfirst) {
-    // z fastest: the workgroups an XCD runs together are consecutive z planes of one (y, x)
-    // column, so each input plane's halo is read by its three z neighbours out of that XCD's
-    // L2 instead of from HBM three times (large planes: 128^2 x 96 channels = 6 MB > 4 MB L2)
-    z = (int)(t % a.D);
-    t /= a.D;
-    tx = (int)(t % a.tiles_x);
-    t /= a.tiles_x;
-    ty = (int)(t % a.tiles_y);
-    b = (int)(t / a.tiles_y);
-  } else {
-    tx = (int)(t % a.tiles_x);
-    t /= a.tiles_x;
-    ty = (int)(t % a.tiles_y);
-    t /= a.tiles_y;
-    z = (int)(t % a.D);
-    b = (int)(t / a.D);
-  }
+  // z fastest: the workgroups an XCD runs together are consecutive z planes of one (y, x)
+  // column, so each input plane's halo is read by its three z neighbours out of that XCD's
+  // L2 instead of from HBM three times (large planes: 128^2 x 96 channels = 6 MB > 4 MB L2)
+  const int z = (int)(t % a.D);
+  t /= a.D;
+  const int tx = (int)(t % a.tiles_x);
+  t /= a.tiles_x;
+  const int ty = (int)(t % a.tiles_y);
+  const int b = (int)(t / a.tiles_y);
   const int x0 = tx * TX, y0 = ty * TY;
   const int co0 = blockIdx.y * (16 * CO_T);
 
@@ -290,9 +279,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_kernel(Conv3Args a) {
         }
       }
       // keep the next step's fragment reads from being hoisted over these MFMAs (VGPRs: the
-      // next chunk's prefetch registers are live across the whole loop); without the split's
-      // lo operands there is room to read one step ahead (WF_CONV_PIPE A/B)
-      if (SPLIT || !PIPE) __builtin_amdgcn_sched_barrier(0);
+      // next chunk's prefetch registers are live across the whole loop)
+      __builtin_amdgcn_sched_barrier(0);
     }
   }
 
@@ -425,22 +413,12 @@ __global__ __launch_bounds__(512, 1) void conv3d_k3w_kernel(Conv3Args a) {
 
   int64_t t = blockIdx.x;
   if ((a.nblocks & 7) == 0) t = (t & 7) * (a.nblocks >> 3) + (t >> 3);
-  int tx, ty, z, b;
-  if (a.zfirst) {
-    z = (int)(t % a.D);
-    t /= a.D;
-    tx = (int)(t % a.tiles_x);
-    t /= a.tiles_x;
-    ty = (int)(t % a.tiles_y);
-    b = (int)(t / a.tiles_y);
-  } else {
-    tx = (int)(t % a.tiles_x);
-    t /= a.tiles_x;
-    ty = (int)(t % a.tiles_y);
-    t /= a.tiles_y;
-    z = (int)(t % a.D);
-    b = (int)(t / a.D);
-  }
+  const int z = (int)(t % a.D);  // z fastest, as conv3d_k3_kernel
+  t /= a.D;
+  const int tx = (int)(t % a.tiles_x);
+  t /= a.tiles_x;
+  const int ty = (int)(t % a.tiles_y);
+  const int b = (int)(t / a.tiles_y);
   const int x0 = tx * TX, y0 = ty * TY;
   const int co0 = blockIdx.y * (16 * CO_T);
 
@@ -799,8 +777,6 @@ static int launch_conv3w(const Conv3Args& a0, int prec, hipStream_t stream) {
   a.nblocks = (int64_t)a.B * a.D * a.tiles_y * a.tiles_x;
   if (a.nblocks >= ((int64_t)1 << 31)) return fail(WF_E_SHAPE, "wf_conv3d_k3_fwd: too many tiles");
   a.ksplit = 1;
-  static const int zf = getenv("WF_CONV_ZFIRST") ? atoi(getenv("WF_CONV_ZFIRST")) : 1;
-  a.zfirst = zf;
   a.dbg = WF_CONV_DBG && getenv("WF_CONV_DBG") ? atoi(getenv("WF_CONV_DBG")) : 0;
   auto kern = a.xh ? conv3d_k3w_kernel<PREC_FP16, true>
               : prec == PREC_SPLIT ? conv3d_k3w_kernel<PREC_SPLIT, false>
@@ -835,23 +811,19 @@ static int launch_conv3(const Conv3Args& a0, int prec, hipStream_t stream) {
   if (a.ksplit == 1 && conv3w_ok(a, prec, wgs)) return launch_conv3w(a0, prec, stream);
   dim3 grid((unsigned)a.nblocks, (unsigned)(a.Cout / (16 * CO_T)), (unsigned)a.ksplit);
   const bool post_stats = a.stats && a.ksplit > 1;  // partial outputs: a separate pass below
-  static const int zf = getenv("WF_CONV_ZFIRST") ? atoi(getenv("WF_CONV_ZFIRST")) : 1;
-  a.zfirst = zf;
   a.dbg = WF_CONV_DBG && getenv("WF_CONV_DBG") ? atoi(getenv("WF_CONV_DBG")) : 0;
-  // WF_CONV_PIPE=1 (A/B): non-split kernels without the per-K-step scheduling fence, so the
-  // next step's fragment reads can be issued under the current step's MFMAs
-  static const bool pipe = getenv("WF_CONV_PIPE") && getenv("WF_CONV_PIPE")[0] == '1';
-  {
-    auto kern = a.xh                ? (pipe ? conv3d_k3_kernel<CO_T, NT, PREC_FP16, true, RW, true>
-                                            : conv3d_k3_kernel<CO_T, NT, PREC_FP16, false, RW, true>)
-                : prec == PREC_SPLIT  ? conv3d_k3_kernel<CO_T, NT, PREC_SPLIT, false, 1>
-                : prec == PREC_FP16 ? (pipe ? conv3d_k3_kernel<CO_T, NT, PREC_FP16, true, RW>
-                                            : conv3d_k3_kernel<CO_T, NT, PREC_FP16, false, RW>)
-                                    : (pipe ? conv3d_k3_kernel<CO_T, NT, PREC_BF16, true, RW>
-                                            : conv3d_k3_kernel<CO_T, NT, PREC_BF16, false, RW>);
-    set_max_lds(reinterpret_cast<const void*>(kern), (int)lds);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, a);
+  void (*kern)(Conv3Args);
+  if constexpr (RW == 2) {  // conv3_plan: fp16 input only
+    if (!a.xh) return fail(WF_E_SHAPE, "wf_conv3d_k3_fwd: two rows per wave need fp16 input");
+    kern = conv3d_k3_kernel<CO_T, NT, PREC_FP16, 2, true>;
+  } else {
+    kern = a.xh                 ? conv3d_k3_kernel<CO_T, NT, PREC_FP16, 1, true>
+           : prec == PREC_SPLIT ? conv3d_k3_kernel<CO_T, NT, PREC_SPLIT>
+           : prec == PREC_FP16  ? conv3d_k3_kernel<CO_T, NT, PREC_FP16>
+                                : conv3d_k3_kernel<CO_T, NT, PREC_BF16>;
   }
+  set_max_lds(reinterpret_cast<const void*>(kern), (int)lds);
+  hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, a);
   int rc = check_launch("wf_conv3d_k3_fwd");
   if (rc) return rc;
   if (a.ksplit > 1) {
@@ -936,9 +908,7 @@ Conv3Plan conv3_plan(int64_t Cout, int64_t W, int precision, bool xh) {
   // W > 32.  Default for fp16 input only: with fp32 input the larger halo's prefetch registers
   // spill (96->48 at 128^3 fp16: 1.82 vs 1.73 ms); the fp16-input variant fits (240 VGPRs) and
   // runs 48->48 at 192^3 in 2.42 vs 2.52 ms (profiles/r3_conv/rw2_xh_ab_192.txt).
-  // WF_CONV_RW=1 / 2 forces one or the other
-  static const int rw = getenv("WF_CONV_RW") ? atoi(getenv("WF_CONV_RW")) : 0;
-  if (W > 32 && precision != PREC_SPLIT && co3 && (rw == 2 || (rw == 0 && xh))) return {3, 4, 2};
+  if (W > 32 && precision != PREC_SPLIT && co3 && xh) return {3, 4, 2};
   const int nt = W > 32 ? 4 : (W > 16 ? 2 : 1);
   return {co3 ? 3 : 1, nt, 1};
 }

@@ -451,8 +451,7 @@ static int dwt_haar_fwd(const float* x, const float* ln_w, const float* ln_b, fl
   };
   // C = 48 (stage 1, the 400 MB launch): 16 lanes x 1 float4 per position instead of 4 x 3
   // (4 idle lanes) -- 32 data VGPRs instead of 96, so the whole grid is resident at once
-  static const bool wide = getenv("WF_DWT_G4") == nullptr;
-  if (wide && C == 48) return go(ic<16>{}, ic<1>{});
+  if (C == 48) return go(ic<16>{}, ic<1>{});
   return dispatch_gv(C / 4, go);
 }
 

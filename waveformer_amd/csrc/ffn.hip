@@ -433,9 +433,7 @@ int launch_dwconv3d(const void* in, const float* w, const float* b, void* out, f
   // z segment: enough workgroups to fill 256 CUs ~8 deep, but long enough that the two halo
   // planes per segment stay a small overhead
   // narrow volumes (W <= 8): 64 channels x 8 columns per workgroup, z segments down to 4
-  // (WF_DW_NARROW=0: the 32 x 16 tiles, A/B)
-  static const bool narrow_ok = !(getenv("WF_DW_NARROW") && getenv("WF_DW_NARROW")[0] == '0');
-  const bool narrow = narrow_ok && W <= 8 && Hd % 64 == 0 && store32(prec) && !flip && !ln1_stats;
+  const bool narrow = W <= 8 && Hd % 64 == 0 && store32(prec) && !flip && !ln1_stats;
   const int dch = narrow ? 64 : DW_CH, dtx = narrow ? 8 : DW_TX;
   const int64_t base = (int64_t)B * (Hd / dch) * cdiv(H, DW_TY) * cdiv(W, dtx);
   int ZS = D;
@@ -626,10 +624,9 @@ extern "C" int wf_ccf_ffn_stage(int stage, const float* xh, const float* stats,
   // K-chunked GEMM with a plain bias epilogue, then one in-place LayerNorm + GELU row pass.
   // Round 5: gemm_lnw with 8 / 16-wave workgroups holds the whole 768 / 1536-wide row (the
   // columns split over the waves), so the LayerNorm + GELU run in its epilogue and the
-  // separate pass is gone (WF_FFN_NO_LNW_WIDE=1: the round-4 split path, A/B)
-  static const bool no_split_ln1 = getenv("WF_FFN_NO_SPLIT_LN1") != nullptr;
-  const bool split_ln1 = !no_split_ln1 && store32(precision) && hidden >= 768 &&
-                         hidden <= 1536 && !(g.a_map == MAP_IDENTITY && gemm_lnw_wide_shape(g));
+  // separate pass is gone for the shapes it takes
+  const bool split_ln1 = store32(precision) && hidden >= 768 && hidden <= 1536 &&
+                         !gemm_lnw_wide_shape(g);
   // C = 48 / hidden = 192 (stage 1), opt-in (WF_FFN_FUSED=1): the whole FFN in one kernel
   // (ffn_fused.hip), h1 and h2 stay on chip; stage 2 is that kernel, stages 1 and 3 are part
   // of it.  Off by default: recomputing the 4 x 8 tile's haloed h1 plane (1.875x the pw GEMM,
@@ -675,8 +672,7 @@ extern "C" int wf_ccf_ffn_stage(int stage, const float* xh, const float* stats,
   float* pw_pst = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + 2 * one + stq);
   float* ln1_st = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + 2 * one + 2 * stq);
   int pw_np = 0;
-  if (split_ln1 && !keep && !ln1_pass && hidden % DW_STAT_GROUP == 0 &&
-      getenv("WF_FFN_FUSED_DW") == nullptr) {
+  if (split_ln1 && !keep && !ln1_pass && hidden % DW_STAT_GROUP == 0) {
     GemmArgs g2 = g;
     g2.epi = EPI_STORE;
     const int nt = gemm_kc_pick_nt(g2);
@@ -703,9 +699,9 @@ extern "C" int wf_ccf_ffn_stage(int stage, const float* xh, const float* stats,
   }
   if (rc) return rc;
   // dwconv + LN2 + GELU (+ fc + residual): the stage-1 and stage-2 shapes run the fused back
-  // half (ffn_dwfc.hip, h2 stays on chip); other shapes either fuse dwconv + LN over the full 4C row
-  // in LDS, or run the z-marching depthwise conv with LN2 + GELU moved into the fc loader
-  static const bool fused_dw = getenv("WF_FFN_FUSED_DW") != nullptr;
+  // half (ffn_dwfc.hip, h2 stays on chip); other shapes run the z-marching depthwise conv with
+  // LN2 + GELU moved into the fc loader, or (hidden % 32 != 0) fuse dwconv + LN over the full 4C
+  // row in LDS
   const bool no_dwfc = getenv("WF_FFN_NO_DWFC") != nullptr;  // per call: tests switch it
   const bool dwfc1 = C == 48 && hidden == 192, dwfc2 = C == 96 && hidden == 384;
   if (!keep && !no_dwfc && (dwfc1 || dwfc2)) {
@@ -729,9 +725,9 @@ extern "C" int wf_ccf_ffn_stage(int stage, const float* xh, const float* stats,
     d.D = (int)D;
     d.H = (int)H;
     d.W = (int)W;
-    return dwfc1 ? launch_ffn_dwfc(d, precision, s) : launch_ffn_dwfc2(d, precision, s);
+    return dwfc1 ? launch_ffn_dwfc_s1(d, precision, s) : launch_ffn_dwfc2(d, precision, s);
   }
-  const bool split_ln = (keep || !fused_dw) && hidden % 32 == 0;
+  const bool split_ln = hidden % 32 == 0;
   WF_REQUIRE(!keep || split_ln, "training needs hidden % 32 == 0 (h2 kept pre-LayerNorm)");
   float* pst = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + 2 * one);
   if (stage == 0 || stage == 2) {

@@ -297,7 +297,7 @@ __global__ __launch_bounds__(ff::NTH, 1) void ffn_fused_kernel(DwFcArgs a) {
 
   auto step = [&](int p, const f32x4& xr_c, const f32x2& es_c, f32x4& xr_n, f32x2& es_n) {
     // ---- S1: scatter plane p into output planes p+1 (kz 0), p (kz 1), p-1 (kz 2)
-    if (!(a.dbg & 1)) {
+    if (!(ffn_dbg(a) & 1)) {
       const float* Pin = u1 + xi * HS + 2 * cp;
 #pragma unroll
       for (int r = 0; r < PY; ++r) {
@@ -325,15 +325,15 @@ __global__ __launch_bounds__(ff::NTH, 1) void ffn_fused_kernel(DwFcArgs a) {
     // would then drain the loads issued just below (vmcnt(0)) before re-using the registers.
     asm volatile("" ::"v"(st0), "v"(st1), "v"(st2), "v"(sst), "v"(xr_c), "v"(es_c));
     f32x4 hacc[4];
-    const bool have = q <= z1 && q >= 0 && q < D && !(a.dbg & 2);
+    const bool have = q <= z1 && q >= 0 && q < D && !(ffn_dbg(a) & 2);
     if (have) pw_plane(hacc);
     // Loads for the next step, issued after the pw consumed this step's: the epilogue rows of
     // output plane p first, then the x rows of plane q + 1.  Both stay in flight behind S3, S4
     // and the next scatter; the compiler's (in-order) vmcnt waits before them only cover loads
     // issued a step earlier.
     if (p >= z0 && p < z1) epi_fetch(p, xr_n, es_n);
-    if (q + 1 <= z1 && !(a.dbg & 32)) fetch(q + 1);
-    if (zo >= z0 && !(a.dbg & 64)) {
+    if (q + 1 <= z1 && !(ffn_dbg(a) & 32)) fetch(q + 1);
+    if (zo >= z0 && !(ffn_dbg(a) & 64)) {
 #pragma unroll
       for (int o = 0; o < TY; ++o) {
         f32x2 h = accA[o] + bias2;
@@ -346,7 +346,7 @@ __global__ __launch_bounds__(ff::NTH, 1) void ffn_fused_kernel(DwFcArgs a) {
     }
     __syncthreads();  // B2: the moments of plane q, the h2 tile visible
     // ---- S3: LN1 + GELU of plane q into u1; LN2 + GELU + split of the h2 tile
-    if (q <= z1 && !(a.dbg & 4)) ln1_store(hacc, have);
+    if (q <= z1 && !(ffn_dbg(a) & 4)) ln1_store(hacc, have);
     int ltid = tid;
     asm volatile("" : "+v"(ltid));
     const int lln = ltid & 63, lwid = ltid >> 6;
@@ -360,7 +360,7 @@ __global__ __launch_bounds__(ff::NTH, 1) void ffn_fused_kernel(DwFcArgs a) {
     const int col = ct * 16 + 4 * lg4;
     const bool fcw_wave = fw >= 0;
     if (zo >= z0) {
-      if (ltid < NPOS * LN_LANES && !(a.dbg & 8)) {
+      if (ltid < NPOS * LN_LANES && !(ffn_dbg(a) & 8)) {
         const int pos = ltid / LN_LANES, gg = ltid % LN_LANES;
         float* row = h2t + pos * HS;
         float v[LN_CH];
@@ -406,7 +406,7 @@ __global__ __launch_bounds__(ff::NTH, 1) void ffn_fused_kernel(DwFcArgs a) {
     }
     __syncthreads();  // B3: plane q ready for the next scatter, LN2 rows visible
     // ---- S4: fc GEMM (the last RT*CT waves) + bias + Q4 residual
-    if (zo >= z0 && fcw_wave && !(a.dbg & 16)) {
+    if (zo >= z0 && fcw_wave && !(ffn_dbg(a) & 16)) {
       f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
       const uint16_t* Bh = reinterpret_cast<const uint16_t*>(h2t) + (size_t)lp * (2 * HS);
       const uint16_t* Wh = fcw + (size_t)(ct * 16 + ll15) * WKP;
@@ -456,8 +456,7 @@ int launch_ffn_fused(const DwFcArgs& a, int prec, hipStream_t s) {
   int ZS = g.D;
   while (ZS > 8 && base * cdiv(g.D, ZS) < 1024) ZS = (ZS + 1) / 2;
   g.ZS = ZS;
-  const char* dbg = getenv("WF_FFN_DBG");  // timing experiments: phases to skip (bit mask)
-  g.dbg = dbg ? atoi(dbg) : 0;
+  g.dbg = ffn_dbg_env();
   const int64_t blocks = base * cdiv(g.D, ZS);
   void (*kern)(DwFcArgs) = prec == PREC_SPLIT ? ffn_fused_kernel<PREC_SPLIT>
                            : prec == PREC_FP16 ? ffn_fused_kernel<PREC_FP16>

@@ -317,20 +317,15 @@ int launch_gemm(const GemmArgs& g, hipStream_t s, const char* who) {
   if (g.a_C % 8 != 0) return fail(WF_E_SHAPE, std::string(who) + ": channels must be a multiple of 8");
   if (g.M <= 0) return WF_OK;
   // streaming kernels first: gemm_rows when one LDS-resident weight chunk covers all N,
-  // else the K-chunked gemm_kc (WF_GEMM_NO_KC: gemm_rows over several column chunks); the A-resident
-  // gemm_ares takes the remaining shapes.  (WF_GEMM_ARES_ONLY / WF_GEMM_NO_KC: A/B switches)
-  static const bool ares_only = getenv("WF_GEMM_ARES_ONLY") != nullptr;
-  static const bool no_kc = getenv("WF_GEMM_NO_KC") != nullptr;
+  // else the K-chunked gemm_kc; the A-resident gemm_ares takes the remaining shapes
   if (g.o_pstats) {  // LayerNorm partials in the epilogue: gemm_kc only
     if (g.epi == EPI_STORE && !g.out_bf16 && !g.a_bf16 && try_launch_gemm_kc(g, s))
       return check_launch(who);
     return fail(WF_E_SHAPE, std::string(who) + ": LN-partial epilogue needs the gemm_kc shape");
   }
-  if (!ares_only) {
-    if (try_launch_gemm_lnw(g, s)) return check_launch(who);
-    if (try_launch_gemm_rows(g, s, !no_kc)) return check_launch(who);
-    if (!no_kc && try_launch_gemm_kc(g, s)) return check_launch(who);
-  }
+  if (try_launch_gemm_lnw(g, s)) return check_launch(who);
+  if (try_launch_gemm_rows(g, s, true)) return check_launch(who);
+  if (try_launch_gemm_kc(g, s)) return check_launch(who);
   const bool split = g.prec == PREC_SPLIT;
   int BM = 64;
   while (BM > 16 && gemm_lds_bytes(BM, g.K, g.N, split) > 80 * 1024) BM >>= 1;

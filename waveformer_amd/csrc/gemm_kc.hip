@@ -36,15 +36,10 @@ struct KcCfg {
   static constexpr int WPT = (WITEMS + NTHR - 1) / NTHR;  // per thread
 };
 
-// KR > 0 (K == 32 KR, LN_COMPUTE, one row tile per wave; PatchMerging 1 -> 2 at K = 384):
-// the lane's whole A row share (KR k-octets, 8 KR floats) is loaded ONCE into registers before
-// the k loop, the LayerNorm moments come from those registers and the (fully unrolled) k loop
-// reads them again -- the round-3 statistics pass and the k loop each streamed the rows, and
-// with 128-row workgroups the second read missed L2 (PMC 2.2x the input bytes)
 // WV = 16 (PatchMerging 1 -> 2, 2048 workgroups of 8 waves): 256-row workgroups, so the weight
 // chunk is staged through LDS once per 256 rows instead of per 128 -- at 128 rows the staged
 // weight bytes (147 KB per workgroup, 302 MB per launch) were 60 % of the A bytes
-template <int NT, int P, int MAP, int EPI, bool ABF16, int KR = 0, int WV = 8>
+template <int NT, int P, int MAP, int EPI, bool ABF16, int WV = 8>
 __global__ __launch_bounds__(64 * WV) void gemm_kc_kernel(GemmArgs g) {
   typedef KcCfg<NT, WV> C;
   constexpr bool SPLIT = P == PREC_SPLIT;  // P: Prec (operand kind)
@@ -116,31 +111,7 @@ __global__ __launch_bounds__(64 * WV) void gemm_kc_kernel(GemmArgs g) {
       rstd[rt] = g.a_stats[2 * arow[rt] + 1];
     }
   }
-  float areg[KR > 0 ? KR : 1][8];
-  if constexpr (KR > 0) {
-    static_assert(C::RT == 1, "register-resident A: one row tile per wave");
-    const RowMapper<MAP> rm(g, arow[0]);
-#pragma unroll
-    for (int ks = 0; ks < KR; ++ks) load8f<ABF16>(g.a_src, rm.offset(g, ks * KC_BK + 8 * g4), areg[ks]);
-    // the same shifted one-pass moments as below, in the same order (octet g4 + 4 ks)
-    const float sh = __shfl(areg[0][0], l15, 64);
-    float s = 0.f, q = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < KR; ++ks)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float d = areg[ks][j] - sh;
-        s += d;
-        q += d * d;
-      }
-    s = xsum16(s);
-    s = xsum32(s);
-    q = xsum16(q);
-    q = xsum32(q);
-    const float ms = s / (float)K;
-    mean[0] = sh + ms;
-    rstd[0] = rsqrtf(fmaxf(q / (float)K - ms * ms, 0.f) + g.a_eps);
-  } else if (g.a_ln == LN_COMPUTE) {
+  if (g.a_ln == LN_COMPUTE) {
     // one pass: sums of x - s and (x - s)^2 with s = the row's first element (keeps the
     // variance free of cancellation when |mean| >> std); the 4 lanes of a row split the k range
 #pragma unroll
@@ -208,7 +179,6 @@ __global__ __launch_bounds__(64 * WV) void gemm_kc_kernel(GemmArgs g) {
   typedef float ARegs[RT][8];
   ARegs an[2];
   auto afetch = [&](int ks, ARegs& dst) {
-    if constexpr (KR > 0) return;
     const int k = min(ks * KC_BK + 8 * g4, K - 8);
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
@@ -305,29 +275,14 @@ __global__ __launch_bounds__(64 * WV) void gemm_kc_kernel(GemmArgs g) {
   };
   typedef std::integral_constant<int, 0> Slot0;
   typedef std::integral_constant<int, 1> Slot1;
-  if constexpr (KR > 0) {
-#pragma unroll
-    for (int ks = 0; ks < KR; ks += 2) {
-      ARegs vin;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) vin[0][j] = areg[ks][j];
-      kbody(ks, Slot0{}, vin);
-      if (ks + 1 < KR) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) vin[0][j] = areg[ks + 1][j];
-        kbody(ks + 1, Slot1{}, vin);
-      }
-    }
-  } else {
-    // both halves unconditional (a conditional second half makes the loop-carried register
-    // sets phis, and their copies wait for the prefetches at every barrier): an odd step
-    // count runs one extra step whose A operands are zeroed (k >= K: the kv select) against a
-    // weight slice re-reading the last octet (finite), adding exact zeros
+  // both halves unconditional (a conditional second half makes the loop-carried register
+  // sets phis, and their copies wait for the prefetches at every barrier): an odd step
+  // count runs one extra step whose A operands are zeroed (k >= K: the kv select) against a
+  // weight slice re-reading the last octet (finite), adding exact zeros
 #pragma unroll 1
-    for (int ks = ks0; ks < ks1; ks += 2) {
-      kbody(ks, Slot0{}, an[0]);
-      kbody(ks + 1, Slot1{}, an[1]);
-    }
+  for (int ks = ks0; ks < ks1; ks += 2) {
+    kbody(ks, Slot0{}, an[0]);
+    kbody(ks + 1, Slot1{}, an[1]);
   }
 
   if (part) {  // raw partials (M, N) of split blockIdx.z; bias and epilogue in the reduce
@@ -489,17 +444,15 @@ __global__ __launch_bounds__(256) void gemm_kc_reduce_kernel(GemmArgs g) {
 // loaders gain nothing (profiles/r6/r6ks*_ab.txt).  The split count is a function of K, N and the
 // precision only -- never of M -- so a row's sum order does not change with the batch (the B = 8
 // graph replay equals per-volume B = 1 forwards, test_gpu_bench_config.py).
-// (WF_KC_SPLIT: the largest split, A/B; 1 disables)
-static int kc_ksplit(const GemmArgs& g, bool areg) {
-  static const int maxs = getenv("WF_KC_SPLIT") ? std::max(1, atoi(getenv("WF_KC_SPLIT"))) : 4;
-  if (!g.kpart || areg || g.o_pstats || !g.a_gelu || (g.epi != EPI_STORE && g.epi != EPI_RESID))
+static int kc_ksplit(const GemmArgs& g) {
+  if (!g.kpart || g.o_pstats || !g.a_gelu || (g.epi != EPI_STORE && g.epi != EPI_RESID))
     return 1;
   if (g.M * (int64_t)(g.N / 4) >= ((int64_t)1 << 31) || g.N % 4 != 0 || g.K < 1536) return 1;
   const int nks = (g.K + KC_BK - 1) / KC_BK;
   // scratch: the caller's kpart_bytes is a multiple of M (the fc's dead h1 = M x hidden), so the
   // fit test below does not depend on M either
   int s = 1;
-  while (2 * s <= std::min(maxs, KC_MAX_SPLIT) && nks / (2 * s) >= 6 &&
+  while (2 * s <= KC_MAX_SPLIT && nks / (2 * s) >= 6 &&
          (int64_t)(2 * s) * g.M * g.N * 4 <= g.kpart_bytes)
     s *= 2;
   if (s == 1) return 1;
@@ -512,17 +465,7 @@ static void go_kc(const GemmArgs& g, hipStream_t s) {
   typedef KcCfg<NT> C;
   const bool split = g.prec == PREC_SPLIT;
   void (*kern)(GemmArgs);
-  // PatchMerging 1 -> 2 (K = 8 x 48): A rows register-resident, opt-in WF_KC_AREG=1 -- one
-  // read of A, but 170 VGPRs (one 8-wave workgroup per CU instead of two) and it measured
-  // 207-210 us against 204 us for the statistics pass + streaming k loop (round 4)
-  static const bool no_areg = getenv("WF_KC_AREG") == nullptr || getenv("WF_KC_AREG")[0] == '0';
-  constexpr bool areg_ok = MAP == MAP_MERGE && EPI == EPI_STORE && NT <= 8;
-  const bool areg = areg_ok && !no_areg && g.K == 12 * KC_BK && g.a_ln == LN_COMPUTE && !g.a_bf16;
-  if (areg)
-    kern = split ? gemm_kc_kernel<NT, PREC_SPLIT, MAP, EPI, false, areg_ok ? 12 : 0>
-                 : (g.prec == PREC_FP16 ? gemm_kc_kernel<NT, PREC_FP16, MAP, EPI, false, areg_ok ? 12 : 0>
-                                        : gemm_kc_kernel<NT, PREC_BF16, MAP, EPI, false, areg_ok ? 12 : 0>);
-  else if (g.a_bf16)  // bf16 activations only exist in PREC_BF16
+  if (g.a_bf16)  // bf16 activations only exist in PREC_BF16
     kern = gemm_kc_kernel<NT, PREC_BF16, MAP, EPI, true>;
   else if (split)
     kern = gemm_kc_kernel<NT, PREC_SPLIT, MAP, EPI, false>;
@@ -530,17 +473,15 @@ static void go_kc(const GemmArgs& g, hipStream_t s) {
     kern = gemm_kc_kernel<NT, PREC_FP16, MAP, EPI, false>;
   else
     kern = gemm_kc_kernel<NT, PREC_BF16, MAP, EPI, false>;
-  // 16-wave workgroups for every grid of >= 1024 8-wave workgroups (default, WF_KC_WV16=1),
-  // PatchMerging only (=2) or none (=0): stage-1 merge 209.8 -> 201.9 us, stage-3 pwconv
-  // 64.2 -> 61.4, config 5 45.6-45.8 -> 46.0 volumes/s (profiles/r4_gemm/)
-  static const int wv16 = getenv("WF_KC_WV16") ? atoi(getenv("WF_KC_WV16")) : 1;
+  // 16-wave workgroups for every grid of >= 1024 8-wave workgroups: stage-1 merge
+  // 209.8 -> 201.9 us, stage-3 pwconv 64.2 -> 61.4, config 5 45.6-45.8 -> 46.0 volumes/s
+  // (profiles/r4_gemm/)
   int rows = C::ROWS, nthr = C::NTHR;
   if constexpr (NT <= 8 && EPI != EPI_LN_GELU) {
-    const bool want = wv16 == 1 || (wv16 == 2 && MAP == MAP_MERGE);
-    if (want && !areg && !g.a_bf16 && cdiv(g.M, C::ROWS) * (g.N / C::NC) >= 1024 &&
+    if (!g.a_bf16 && cdiv(g.M, C::ROWS) * (g.N / C::NC) >= 1024 &&
         (split || g.prec == PREC_FP16)) {
-      kern = split ? gemm_kc_kernel<NT, PREC_SPLIT, MAP, EPI, false, 0, 16>
-                   : gemm_kc_kernel<NT, PREC_FP16, MAP, EPI, false, 0, 16>;
+      kern = split ? gemm_kc_kernel<NT, PREC_SPLIT, MAP, EPI, false, 16>
+                   : gemm_kc_kernel<NT, PREC_FP16, MAP, EPI, false, 16>;
       rows = KcCfg<NT, 16>::ROWS;
       nthr = KcCfg<NT, 16>::NTHR;
     }
@@ -548,7 +489,7 @@ static void go_kc(const GemmArgs& g, hipStream_t s) {
   GemmArgs gk = g;
   gk.ksplit = 1;
   if constexpr (EPI == EPI_STORE || EPI == EPI_RESID)
-    gk.ksplit = kc_ksplit(g, areg);
+    gk.ksplit = kc_ksplit(g);
   const int nks = (int)cdiv(g.K, KC_BK);
   const int nks2 = gk.ksplit > 1 ? ((nks + 2) & ~1) : ((nks + 1) & ~1);  // as the kernel's
   const size_t lds = (size_t)2 * (split ? 2 : 1) * C::NC * KC_KP * 2 +
@@ -587,14 +528,13 @@ int gemm_kc_pick_nt(const GemmArgs& g) {
   if (!known) return 0;
   const int tiles = g.N / 16;
   static const int cand[] = {24, 12, 8, 6, 4, 3, 2, 1};
-  // narrowest chunk the small-M search may go down to (WF_KC_MINNT, A/B; round 1-4: 3)
-  static const char* env_minnt = getenv("WF_KC_MINNT");
-  int minnt = env_minnt ? std::max(1, atoi(env_minnt)) : 3;
+  // narrowest chunk the small-M search may go down to
+  int minnt = 3;
   // loaders with a costly A transform (the fc's LayerNorm + GELU, the window gather + LN of qkv)
   // redo it per column chunk: at N >= 384 (8+ chunks of 3 tiles) 6-tile chunks halve that work
   // (stage-4 qkv 52.3 -> 39.0 us, the 576-column qkv 16.1 -> 13.4 us; plain loaders measured
   // slower with fewer chunks, profiles/r6/r6ks2_ab.txt)
-  if (!env_minnt && (g.a_gelu || g.a_map == MAP_WINDOW) && g.N >= 384) minnt = 6;
+  if ((g.a_gelu || g.a_map == MAP_WINDOW) && g.N >= 384) minnt = 6;
   // the split-K fc (kc_ksplit: GELU loader, K >= 1536, caller scratch): the widest chunk up to
   // 12 tiles -- 2 chunks of 192 at stage 4, 256 workgroups with the 4 k splits: 55.5 -> 48.0 us
   // per B = 8 launch against 6 tiles; at stage 3 (no split) one 12-tile chunk measured 71 -> 73.5

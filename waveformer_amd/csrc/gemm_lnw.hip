@@ -28,7 +28,7 @@ namespace wf {
 // measured slower than gemm_rows (909 vs 974 volumes/s: K = 48 pads to two 32-wide K-steps
 // and the A staging is exposed).  Round 5: the wide rows of stages 3 / 4 (N = 768 on 8 waves,
 // 1536 on 16) -- the whole row in one workgroup, so the LayerNorm + GELU epilogue replaces
-// the K-chunked GEMM + separate ln_act pass (a read and a write of h1)
+// the K-chunked GEMM + separate ln_act pass (a read and a write of h1); only N = 768 is kept
 template <int NWV> struct LnwBounds { static constexpr int MINW = NWV == 4 ? 2 : 1; };
 template <int P, int KS, int LW_NTW, int LW_RT, int NWV = 4>
 __global__ __launch_bounds__(NWV * 64, LnwBounds<NWV>::MINW) void gemm_lnw_kernel(GemmArgs g) {
@@ -219,44 +219,28 @@ void go_lnw(const GemmArgs& g, hipStream_t s) {
 // the wide-row shapes this kernel takes: the stage-3 pwconv N = 768 (K <= 192) -- 78.7 us
 // against 61.6 + 43.9 for gemm_kc + ln_act_fwd at B = 8 (profiles/r5_lnw_wide_ab.txt).  The
 // stage-4 N = 1536 on 16 waves measured 81.9 against 29.3 + 21.2 (256 workgroups of 16 rows
-// each streaming the 2.4 MB weight: latency-bound), so it stays on the split path unless
-// WF_LNW_WIDE1536=1
-bool gemm_lnw_wide_shape(const GemmArgs& g) {
-  static const bool off = getenv("WF_FFN_NO_LNW_WIDE") != nullptr;  // A/B switch
-  static const bool w1536 = getenv("WF_LNW_WIDE1536") != nullptr;
-  const int ks = (g.K + 31) / 32;
-  return !off && ((g.N == 768 && ks == 6) || (w1536 && g.N == 1536 && ks == 12));
-}
+// each streaming the 2.4 MB weight: latency-bound), so it stays on the split path
+bool gemm_lnw_wide_shape(const GemmArgs& g) { return g.N == 768 && (g.K + 31) / 32 == 6; }
 
 int try_launch_gemm_lnw(const GemmArgs& g, hipStream_t s) {
-  static const bool off = getenv("WF_GEMM_NO_LNW") != nullptr;  // A/B switch
-  if (off || g.epi != EPI_LN_GELU || g.a_map != MAP_IDENTITY || g.a_bf16 || g.a_gelu ||
+  if (g.epi != EPI_LN_GELU || g.a_map != MAP_IDENTITY || g.a_bf16 || g.a_gelu ||
       !(g.a_ln == LN_NONE || g.a_ln == LN_GIVEN) || g.a_C != g.K || g.K % 8 != 0 ||
       g.M >= ((int64_t)1 << 31) || g.ldo < g.N || g.ldo % 4 != 0)
     return 0;
   if (try_launch_pw2_resident(g, s)) return 1;
   const int ks = (g.K + 31) / 32;
-  static const int wrt = getenv("WF_LNW_WIDE_RT") ? atoi(getenv("WF_LNW_WIDE_RT")) : 4;
   if (gemm_lnw_wide_shape(g)) {
-    if (g.N == 768) {
-      if (wrt == 2) go_lnw<6, 6, 2, 8>(g, s);
-      else go_lnw<6, 6, 4, 8>(g, s);
-    } else {
-      go_lnw<12, 6, 1, 16>(g, s);
-    }
+    go_lnw<6, 6, 4, 8>(g, s);
     return 1;
   }
   if (g.N == 384) {
-    // WF_LNW384: the stage-2 shape's (column tiles, row tiles, waves) -- 0: (6, 4, 4) (round
-    // 2, 200.2-201.1 us at B = 8), 1: (3, 4, 8) (196.0), 2 (default): (3, 8, 8), 128 rows per
-    // workgroup, the weight streamed once per 128 rows (194.5; profiles/r5_lnw_wide_ab.txt)
-    static const int v384 = getenv("WF_LNW384") ? atoi(getenv("WF_LNW384")) : 2;
-    if (ks == 3 && v384 == 1) { go_lnw<3, 3, 4, 8>(g, s); return 1; }
-    if (ks == 3 && v384 == 2) { go_lnw<3, 3, 8, 8>(g, s); return 1; }
+    // the stage-2 shape (K = 96): (column tiles, row tiles, waves) = (3, 8, 8), 128 rows per
+    // workgroup, the weight streamed once per 128 rows -- 194.5 us at B = 8 against 200.2-201.1
+    // for (6, 4, 4) and 196.0 for (3, 4, 8) (profiles/r5_lnw_wide_ab.txt)
     switch (ks) {
       case 1: go_lnw<1, 6, 4>(g, s); return 1;
       case 2: go_lnw<2, 6, 4>(g, s); return 1;
-      case 3: go_lnw<3, 6, 4>(g, s); return 1;
+      case 3: go_lnw<3, 3, 8, 8>(g, s); return 1;
       case 4: go_lnw<4, 6, 4>(g, s); return 1;
       default: return 0;
     }

@@ -28,7 +28,7 @@
 
 namespace wf {
 
-// NTH = 768 (LN + GELU epilogue with fp32 output; WF_GEMM_ROWS_12W=0 for the 8-wave one): 12 waves per
+// NTH = 768 (LN + GELU epilogue with fp32 output): 12 waves per
 // workgroup, three per SIMD -- the epilogue's LayerNorm / GELU VALU work needs three waves to
 // reach the SIMD's issue rate (tools/ubench_valu.hip); the output restaging then goes through
 // LDS 8 rows at a time so 12 waves' staging buffers fit next to the weight chunk
@@ -438,11 +438,10 @@ __global__ __launch_bounds__(NTH) void gemm_rows_kernel(GemmArgs g) {
   }
 }
 
-// the 12-wave LN + GELU variant (fp32 output, identity rows): default since round 4 (446 vs
-// 452-453 us per stage-1 launch at B = 8); WF_GEMM_ROWS_12W=0 for the 8-wave one
+// the 12-wave LN + GELU variant (fp32 output, identity rows; 446 vs 452-453 us per stage-1
+// launch at B = 8 for the 8-wave one, which bf16 storage keeps)
 static bool rows_w12(const GemmArgs& g) {
-  static const bool w12 = getenv("WF_GEMM_ROWS_12W") == nullptr || getenv("WF_GEMM_ROWS_12W")[0] != '0';
-  return w12 && g.epi == EPI_LN_GELU && g.a_map == MAP_IDENTITY && !g.a_bf16 && g.prec != PREC_BF16;
+  return g.epi == EPI_LN_GELU && g.a_map == MAP_IDENTITY && !g.a_bf16 && g.prec != PREC_BF16;
 }
 
 template <int NT, int MAP, int EPI>
@@ -459,8 +458,10 @@ static void go_rows(const GemmArgs& g0, dim3 grid, size_t lds, hipStream_t s) {
       hipLaunchKernelGGL(kern, dim3(gx, grid.y), dim3(768), lds, s, g);
       return;
     }
-  }
-  if (g.a_bf16)  // bf16 activations only exist in PREC_BF16
+    // bf16 storage (PREC_BF16; bf16 activations only exist there)
+    kern = g.a_bf16 ? gemm_rows_kernel<NT, PREC_BF16, MAP, EPI, true>
+                    : gemm_rows_kernel<NT, PREC_BF16, MAP, EPI, false>;
+  } else if (g.a_bf16)  // bf16 activations only exist in PREC_BF16
     kern = gemm_rows_kernel<NT, PREC_BF16, MAP, EPI, true>;
   else if (g.prec == PREC_SPLIT)
     kern = gemm_rows_kernel<NT, PREC_SPLIT, MAP, EPI, false>;
@@ -508,12 +509,7 @@ int try_launch_gemm_rows(const GemmArgs& g, hipStream_t s, bool single_chunk_onl
   static const int cand[] = {12, 9, 8, 6, 4, 3, 2, 1};
   // the transposed conv's N = 8 Cout is wide: one workgroup per CU holding half the columns
   // reads A twice instead of six times at 64 KB
-  // WF_ROWS_WIDE=1 (A/B): PatchMerging's whole 8C -> 2C weight (150 KB at 1 -> 2) resident in
-  // one workgroup per CU, persistent over row tiles, no barrier in the k loop (gemm_kc streams
-  // the weight through LDS a k-step at a time)
-  static const bool wide = getenv("WF_ROWS_WIDE") && getenv("WF_ROWS_WIDE")[0] == '1';
-  const size_t wbudget = g.epi == EPI_SUBVOXEL ? 136 * 1024
-                         : (wide && g.a_map == MAP_MERGE) ? 152 * 1024 : 64 * 1024;
+  const size_t wbudget = g.epi == EPI_SUBVOXEL ? 136 * 1024 : 64 * 1024;
   int nt = 0;
   for (int c : cand) {
     if (tiles % c != 0) continue;

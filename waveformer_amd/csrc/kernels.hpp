@@ -206,13 +206,19 @@ struct DwFcArgs {
   const float* ln1_w;    // (HID)
   const float* ln1_b;
   float eps1;
-  int dbg;               // timing experiments only (WF_FFN_DBG): bit mask of phases skipped
-  int ws_split;          // wave-specialised ffn_dwfc: D rows of a plane in phase 1 (1..5)
+  int dbg;               // timing experiments only (builds with WF_FFN_DBG=1): phases skipped
 };
-int launch_ffn_dwfc(const DwFcArgs& a, int prec, hipStream_t s);
-// stage-1 shape, three VALU waves per SIMD and one barrier per plane (ffn_dwfc_tb.hip)
-int launch_ffn_dwfc_tb(const DwFcArgs& a, int prec, hipStream_t s);
-// the same on 4 x 8 tiles with two barriers per plane (ffn_dwfc_tb.hip, WF_FFN_DWFC_TB=4)
+#ifndef WF_FFN_DBG  // 1: timing-experiment build (DwFcArgs::dbg phase skips; never the shipped library)
+#define WF_FFN_DBG 0
+#endif
+// the phases a kernel skips: none unless the build has WF_FFN_DBG=1 (results are then invalid)
+__device__ __forceinline__ int ffn_dbg(const DwFcArgs& a) { return WF_FFN_DBG ? a.dbg : 0; }
+inline int ffn_dbg_env() {
+  return WF_FFN_DBG && getenv("WF_FFN_DBG") ? atoi(getenv("WF_FFN_DBG")) : 0;
+}
+// stage-1 shape: ffn_dwfc_tb4 for fp32 h1 and outputs below 2 GiB, else ffn_dwfc_sb
+int launch_ffn_dwfc_s1(const DwFcArgs& a, int prec, hipStream_t s);
+// three VALU waves per SIMD on 4 x 8 tiles, two barriers per plane (ffn_dwfc_tb.hip)
 int launch_ffn_dwfc_tb4(const DwFcArgs& a, int prec, hipStream_t s);
 // h1 plane staging: fp32 (SPLIT / FP16 workspaces) or bf16 (BF16) rows widened to fp32
 template <typename T>

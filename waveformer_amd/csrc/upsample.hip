@@ -169,7 +169,6 @@ __global__ __launch_bounds__(256) void resample_cf_kernel(const float* __restric
 // squares of the outputs (GroupNorm(C, C) statistics, as wf_dwconv3d_stats_cl).
 constexpr int UD_CH = 32, UD_TX = 16, UD_TY = 8, UD_SX = 12, UD_SY = 7;
 
-template <bool PF>
 __global__ __launch_bounds__(256) void upsample_dwconv3d_kernel(
     const float* __restrict__ in, const float* __restrict__ w, const float* __restrict__ bias,
     float* __restrict__ out, double* __restrict__ cstats, int C, int d, int h, int wd, int D,
@@ -210,7 +209,7 @@ __global__ __launch_bounds__(256) void upsample_dwconv3d_kernel(
 
   const float* src = in + (int64_t)b * d * h * wd * C + c0;
   // step 1 loads: Q item i -> (source row sr, source column sj, vector v); the two z source
-  // planes' vectors (PF: in registers during the previous plane's arithmetic)
+  // planes' vectors (in registers during the previous plane's arithmetic)
   f32x4 ld[NQ][2];
   Src1 szp;
   auto fetch = [&](int p) {
@@ -284,9 +283,9 @@ __global__ __launch_bounds__(256) void upsample_dwconv3d_kernel(
   __syncthreads();
   int buf = 0;
   for (int p = z0 - 1; p <= z1; ++p) {
-    // PF: the next plane's source vectors in flight during this plane's arithmetic (24 more
-    // registers); otherwise loaded after it
-    if (PF) fetch(p + 1);
+    // the next plane's source vectors in flight during this plane's arithmetic (24 more
+    // registers)
+    fetch(p + 1);
     const float* P = pl[buf] + xi * CH + 2 * cp;
 #pragma unroll
     for (int r = 0; r < PY; ++r) {
@@ -326,7 +325,6 @@ __global__ __launch_bounds__(256) void upsample_dwconv3d_kernel(
       accB[o] = accC[o];
       accC[o] = f32x2{0.f, 0.f};
     }
-    if (!PF) fetch(p + 1);
     commit_q();  // Q's last readers (interp) finished before the previous barrier
     __syncthreads();
     interp(buf ^ 1, p + 1);  // pl[buf ^ 1]'s last readers finished before the previous barrier
@@ -432,8 +430,7 @@ static int upsample_cl_launch(const float* in, float* out, int64_t B, int64_t C,
   WF_REQUIRE_PTR(in);
   WF_REQUIRE_PTR(out);
   const size_t lds = (size_t)w * C * sizeof(float);
-  static const bool gather = getenv("WF_UPSAMPLE_GATHER") != nullptr;  // A/B: the old kernel
-  if (lds <= 64 * 1024 && !gather) {
+  if (lds <= 64 * 1024) {  // else the gather kernel
     auto k = add ? upsample_cl_lds_kernel<true> : upsample_cl_lds_kernel<false>;
     hipLaunchKernelGGL(k, dim3((unsigned)(B * D * H)), dim3(256), lds, (hipStream_t)stream, in,
                        out, (int)C, (int)d, (int)h, (int)w, (int)D, (int)H, (int)W,
@@ -506,9 +503,7 @@ extern "C" int wf_upsample_dwconv3d_stats_cl(const float* in, const float* w, co
   while (ZS > 8 && base * cdiv(D, ZS) < 2048) ZS = (ZS + 1) / 2;
   const int64_t blocks = base * cdiv(D, ZS);
   WF_REQUIRE(blocks < ((int64_t)1 << 31), "grid too large");
-  static const int pf = getenv("WF_UPDW_PF") ? atoi(getenv("WF_UPDW_PF")) : 1;  // A/B
-  auto k = pf ? upsample_dwconv3d_kernel<true> : upsample_dwconv3d_kernel<false>;
-  hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(256), 0, s, in, w, bias, out, stats_acc,
+  hipLaunchKernelGGL(upsample_dwconv3d_kernel, dim3((unsigned)blocks), dim3(256), 0, s, in, w, bias, out, stats_acc,
                      (int)C, (int)d, (int)h, (int)wd, (int)D, (int)H, (int)W, (int)ZS,
                      align_corners, scz, scy, scx);
   return check_launch("wf_upsample_dwconv3d_stats_cl");

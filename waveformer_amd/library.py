@@ -23,7 +23,6 @@ outputs are empty and the backward raises.  Arithmetic precision is an explicit 
 from __future__ import annotations
 
 import ctypes
-import os
 import weakref
 from typing import List, Optional, Sequence, Tuple
 
@@ -246,14 +245,9 @@ def _attn_setup(ctx, inputs, output):
     ctx.set_materialize_grads(False)  # no zero gradients for the workspace / lse outputs
 
 
-_BLAS_WGRAD = os.environ.get("WF_TRAIN_BLAS_WGRAD") == "1"
-
-
 def _wgrad(dy: Tensor, x: Tensor) -> Tensor:
     """dW = dy^T x over the position rows: wf_gemm_tn (bf16x3 MFMAs, deterministic split over
-    the rows); WF_TRAIN_BLAS_WGRAD=1 keeps the platform BLAS's fp32 GEMM (A/B only)."""
-    if _BLAS_WGRAD:
-        return dy.t().mm(x)
+    the rows)."""
     return ops.gemm_tn(dy, x)
 
 

@@ -9,7 +9,6 @@ PosCNN, PatchEmbed) are kept as plain PyTorch modules so the reference import su
 from __future__ import annotations
 
 import math
-import os
 import threading
 from typing import Optional, Tuple
 
@@ -46,9 +45,6 @@ def _std_init(m: nn.Module) -> None:
     else:
         _conv_fan_out_init(m)
 
-
-# WF_UPDW=0 (A/B): ProjectionUpsample stores the up-sampled tensor and convolves it after
-_UPDW = os.environ.get("WF_UPDW", "1") != "0"
 
 class DropPath(nn.Module):
     """Per-sample stochastic depth (timm semantics).  Block never calls forward(): it asks for
@@ -148,8 +144,7 @@ class ProjectionUpsample(nn.Module):
         dw = self.conv1[1]
         # up-sampling fused into the depthwise conv's plane staging (the 8x / 64x larger
         # up-sampled tensor is never written and re-read), GroupNorm statistics in its epilogue
-        r = ops.upsample_dwconv3d_cl(xc, size, dw.weight, dw.bias, self.norm.eps) \
-            if _UPDW else None
+        r = ops.upsample_dwconv3d_cl(xc, size, dw.weight, dw.bias, self.norm.eps)
         if r is not None:
             y, st = r
         elif dw.bias is not None and C % 32 == 0:
@@ -372,32 +367,9 @@ class WaveletTransform3D(nn.Module):
         return cur.permute(0, 4, 1, 2, 3), list(reversed(yh))
 
 
-# Inference: the attention passes of a multi-scale Block's wavelet levels are independent
-# until the fuse, so the coarser levels (their DWTs and attention chains, small grids that
-# leave most CUs idle) run on a side stream beside the finest level's attention -- forked from
-# and joined back into the current stream, so they are captured as parallel branches of the
-# bench's HIP graph.  Opt-in (WF_MS_STREAMS=1): at B = 8 the finest level's attention
-# (1536 workgroups, two per CU) leaves no CU slots for the side branch until its tail, and the
-# bench measured no gain beyond noise (1117.6 / 1113.4 vs 1118.5 / 1108.4 volumes/s).
-_MS_STREAMS = os.environ.get("WF_MS_STREAMS", "0") == "1"
 # per-thread {id(Block): level-1 LL or None} of the Blocks whose hf the running encoder
 # forward discards (see Block._hf_unused)
 HF_SKIP = threading.local()
-_SIDE = {}
-
-
-def _side_stream(dev: torch.device):
-    """The per-device side stream, created outside graph capture (None while capturing before
-    one exists: the caller then stays on one stream)."""
-    s = _SIDE.get(dev.index)
-    if s is None and not torch.cuda.is_current_stream_capturing():
-        s = _SIDE[dev.index] = torch.cuda.Stream(dev)
-    return s
-
-
-def _concurrent_levels(x: torch.Tensor) -> bool:
-    return (_MS_STREAMS and x.is_cuda and not torch.is_grad_enabled()
-            and not torch.compiler.is_compiling())
 
 
 class Block(nn.Module):
@@ -518,25 +490,8 @@ class Block(nn.Module):
                 srcs = [self.attn.forward_raster(ll) for ll in self._ll_levels(x, ln1, n)]
                 xh, stats = _OPS.msfuse(srcs, x, s_attn, float(self.norm2.eps), True)
                 return ffn_op(xh, stats, self.norm2, self.mlp, s_mlp), ()
-            side = _side_stream(x.device) if n > 1 and _concurrent_levels(x) else None
-            if side is None:
-                bands = self._levels(x, ln1, n)
-                srcs = [self.attn.forward_raster(b[0]) for b in bands]
-            else:
-                # level 1 on this stream; levels 2..n (DWT chain + attention) on the side stream
-                main = torch.cuda.current_stream(x.device)
-                bands = self._levels(x, ln1, 1)
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    cur, rest = bands[0][0], []
-                    for _ in range(n - 1):
-                        b = _OPS.dwt3d(cur, None, None, 0.0).unbind(0)
-                        rest.append(b)
-                        cur = b[0]
-                    rest_srcs = [self.attn.forward_raster(b[0]) for b in rest]
-                srcs = [self.attn.forward_raster(bands[0][0])] + rest_srcs
-                main.wait_stream(side)
-                bands = bands + rest
+            bands = self._levels(x, ln1, n)
+            srcs = [self.attn.forward_raster(b[0]) for b in bands]
             hfs = [ops.bands_to_coeffs(b)[1] for b in bands]
         else:
             srcs = [self.attn.forward_raster(x, ln1)]

@@ -8,7 +8,6 @@ is proj_out's transposed write of each stage output to NCDHW (the tensors the de
 from __future__ import annotations
 
 import math
-import os
 import time
 from typing import List, Tuple
 
@@ -21,10 +20,6 @@ from .. import ops
 from ..blocks import PatchEmbed as _MonaiPatchEmbed
 from . import wave_helper as WH
 from .wave_helper import Block, PatchMerging
-
-
-# WF_HF_SKIP=0 (A/B): every Block computes its detail bands, as the reference does
-_HF_SKIP = os.environ.get("WF_HF_SKIP", "1") != "0"
 
 
 class MultiscaleTransformer(nn.Module):
@@ -124,7 +119,7 @@ class MultiscaleTransformer(nn.Module):
         b0 = self.block1[0]
         if train:
             x = wfa.PatchEmbedFn.apply(x_rgb.contiguous(), pe.weight.contiguous(), pe.bias)
-        elif (_HF_SKIP and len(self.block1) > 1 and b0.ms_attention and b0.level > 0
+        elif (len(self.block1) > 1 and b0.ms_attention and b0.level > 0
               and x_rgb.is_cuda and not torch.compiler.is_compiling()):
             r = ops.patch_embed_ll(x_rgb.contiguous(), pe.weight.contiguous(), pe.bias,
                                    (b0.norm1.weight, b0.norm1.bias, b0.norm1.eps))
@@ -141,7 +136,7 @@ class MultiscaleTransformer(nn.Module):
             for i, blk in enumerate(blocks):
                 # only the stage's last Block's hf is kept (waveformer.py:288-292): the others
                 # run the LL-only DWT in inference
-                skip = _HF_SKIP and not train and i < len(blocks) - 1
+                skip = not train and i < len(blocks) - 1
                 WH.HF_SKIP.blocks = {id(blk): ll0 if s == 0 and i == 0 else None} if skip else {}
                 try:
                     r = blk(x)

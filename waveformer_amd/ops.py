@@ -1143,20 +1143,11 @@ def linear_rows(x2d: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Te
     return out
 
 
-_GEMM_FALLBACK_TRACE = os.environ.get("WF_GEMM_FALLBACK_TRACE") == "1"  # diagnostics
-
-
 def mfma_gemm_ok(a: torch.Tensor, K: int, N: int) -> bool:
     """True when a (M, K) row matrix times a (K, N) operand can run on the streaming MFMA GEMM
     (wf_linear_fwd: K % 8 == 0, N % 4 == 0, a contiguous fp32 on the GPU)."""
-    ok = (a.is_cuda and a.dtype == torch.float32 and a.dim() == 2 and a.is_contiguous()
-          and K % 8 == 0 and K >= 8 and N % 4 == 0 and N >= 4)
-    if not ok and _GEMM_FALLBACK_TRACE:
-        import traceback
-        print(f"[wf] GEMM fallback: a {tuple(a.shape)} stride {a.stride()} {a.dtype} "
-              f"contiguous={a.is_contiguous()} K={K} N={N}", flush=True)
-        traceback.print_stack(limit=6)
-    return ok
+    return (a.is_cuda and a.dtype == torch.float32 and a.dim() == 2 and a.is_contiguous()
+            and K % 8 == 0 and K >= 8 and N % 4 == 0 and N >= 4)
 
 
 def smallk_ok(a: torch.Tensor, K: int, N: int) -> bool:
