@@ -1,6 +1,9 @@
-"""Per-phase cycles of one ffn_dwfc2 workgroup (stage-2 CCF_FFN back half), from a library built
-with -DWF_DWFC2_PROBE (make ... EXTRA=-DWF_DWFC2_PROBE, loaded via WAVEFORMER_HIP_LIB): for each
-of the 12 waves, cycles per plane in each phase between the 3 barriers (work, then wait)."""
+"""Per-phase cycles of one workgroup of the stage-2 CCF_FFN back half, from a library built with
+-DWF_DWFC2_PROBE (make ... EXTRA=-DWF_DWFC2_PROBE, loaded via WAVEFORMER_HIP_LIB): for each wave,
+cycles per plane in each phase between the 3 barriers (work, then wait).  Prints the table of
+whichever kernel ran: ffn_dwfc2_tb (16 waves; its role, 0..11 D and 12..15 E, in the last
+column) or ffn_dwfc2_kernel (12 waves; WAVEFORMER_PRECISION=bf16, or a library without
+ffn_dwfc2_tb)."""
 import ctypes
 import os
 import sys
@@ -12,6 +15,7 @@ import waveformer_amd.network_models as NM  # noqa: E402
 from waveformer_amd import _lib, ops  # noqa: E402
 
 B, C, S = 8, 96, 32
+ops.set_precision(os.environ.get("WAVEFORMER_PRECISION", "bf16x3"))
 torch.manual_seed(0)
 mlp = NM.CCF_FFN(C, 4 * C, img_size=(S, S, S)).cuda().eval()
 norm2 = torch.nn.LayerNorm(C, eps=1e-6).cuda()
@@ -20,11 +24,22 @@ xh, stats = ops.msfuse([], x, 1e-6)
 for _ in range(3):
     ops.ccf_ffn(xh, stats, norm2, mlp)
 torch.cuda.synchronize()
-buf = (ctypes.c_longlong * 96)()
-assert _lib.load().wf_debug_dwfc2_probe(buf) == 0
-names = ["C-A work", "A wait", "A-B work", "B wait", "B-C work", "C wait"]
+lib = _lib.load()
+NAMES12 = ["C-A work", "A wait", "A-B work", "B wait", "B-C work", "C wait"]
+# ffn_dwfc2_tb has a fourth barrier A' between A and B (slot 7: A -> A' work + wait)
+NAMES16 = ["C-A work", "A wait", "A-A' all", "A'-B work", "B wait", "B-C work", "C wait"]
 planes = S + 2
-print("wave  " + "  ".join(f"{n:>9}" for n in names) + "   total  (cycles per plane)")
-for w in range(12):
-    v = [buf[w * 8 + i] / planes for i in range(6)]
-    print(f"{w:4d}  " + "  ".join(f"{c:9.0f}" for c in v) + f"  {sum(v):7.0f}", flush=True)
+for sym, waves in (("wf_debug_dwfc2tb_probe", 16), ("wf_debug_dwfc2_probe", 12)):
+    if not hasattr(lib, sym):
+        continue
+    buf = (ctypes.c_longlong * (waves * 8))()
+    assert getattr(lib, sym)(buf) == 0
+    if not any(buf[w * 8 + i] for w in range(waves) for i in range(6)):
+        continue
+    names, slots = (NAMES16, (0, 1, 7, 2, 3, 4, 5)) if waves == 16 else (NAMES12, range(6))
+    print(sym)
+    print("wave  " + "  ".join(f"{n:>9}" for n in names) + "   total  (cycles per plane)  role")
+    for w in range(waves):
+        v = [buf[w * 8 + i] / planes for i in slots]
+        print(f"{w:4d}  " + "  ".join(f"{c:9.0f}" for c in v) + f"  {sum(v):7.0f}  {buf[w * 8 + 6]:4d}",
+              flush=True)

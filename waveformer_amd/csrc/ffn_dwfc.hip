@@ -15,6 +15,8 @@
 // and is rewritten as bf16 hi / lo MFMA operands, and the fc runs as 16 x 16 MFMA tiles whose
 // epilogue adds bias + the Q4 residual.  The default stage-1 kernel is ffn_dwfc_tb4
 // (ffn_dwfc_tb.hip); ffn_dwfc_sb below serves PREC_BF16 and outputs of 2 GiB and above.
+// Likewise for the stage-2 shape (C = 96, hidden = 384): the default is ffn_dwfc2_tb
+// (ffn_dwfc2_tb.hip); ffn_dwfc2_kernel below serves PREC_BF16 and tensors of 2 GiB and above.
 #include "kernels.hpp"
 
 namespace wf {
@@ -40,23 +42,8 @@ __device__ long long g_dwfc2_probe[12 * 8];
 extern "C" int wf_debug_dwfc2_probe(long long* host) {
   return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_dwfc2_probe), sizeof(g_dwfc2_probe));
 }
-#define PROBE_DECL                                                              \
-  const bool probe_on = blockIdx.x == 0;                                         \
-  long long pr_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pr_last = __builtin_amdgcn_s_memtime();
-#define PROBE(i)                                                                \
-  if (probe_on) {                                                               \
-    const long long t_ = __builtin_amdgcn_s_memtime();                          \
-    pr_acc[i] += t_ - pr_last;                                                  \
-    pr_last = t_;                                                               \
-  }
-#define PROBE_DUMP                                                              \
-  if (probe_on && (tid & 63) == 0)                                              \
-    for (int i_ = 0; i_ < 8; ++i_) g_dwfc2_probe[wid * 8 + i_] = pr_acc[i_];
-#else
-#define PROBE_DECL
-#define PROBE(i)
-#define PROBE_DUMP
 #endif
+#define PROBE_DUMP PROBE_DUMP_TO(g_dwfc2_probe)
 
 // ---------------------------------------------------------------------------------------
 // SIMD-balanced variant (round 3): the same tile, planes and h2 tiles, but the
@@ -836,6 +823,10 @@ int launch_ffn_dwfc2(const DwFcArgs& a, int prec, hipStream_t s) {
   while (ZS > 8 && base * cdiv(g.D, ZS) < 512) ZS = (ZS + 1) / 2;
   g.ZS = ZS;
   g.dbg = ffn_dbg_env();
+  // ffn_dwfc2_tb reads fp32 h1 and addresses x, out and the h1 plane through 32-bit buffer
+  // offsets (2 GiB): bf16 h1 and larger tensors (stage 2 of a 128^3 input at B >= 171) keep
+  // ffn_dwfc2_kernel, which has no such limit
+  if (prec != PREC_BF16 && ffn_dwfc2_tb_fits(g)) return launch_ffn_dwfc2_tb(g, prec, s);
   const int64_t blocks = base * cdiv(g.D, ZS);
   void (*kern)(DwFcArgs) = prec == PREC_SPLIT  ? ffn_dwfc2_kernel<PREC_SPLIT, float>
                            : prec == PREC_FP16 ? ffn_dwfc2_kernel<PREC_FP16, float>

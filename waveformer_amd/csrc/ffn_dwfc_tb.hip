@@ -44,11 +44,6 @@ namespace wf {
 #define WF_TB_EPRIO 3
 #endif
 
-__device__ __forceinline__ int tb_simd_id() {
-  // HW_ID (hwreg 4) bits [5:4]: the SIMD the wave runs on
-  return (int)((__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4)) & 3);
-}
-
 namespace tb4 {
 constexpr int S2 = 4;  // input rows the third D wave of a SIMD scatters in phase 1
 constexpr int C = 48, HID = 192, TY = 4, TX = 8;

@@ -243,8 +243,40 @@ struct H1Load<uint16_t> {
   }
 };
 
-// the same for C = 96, hidden = 384 (4 x 4 tiles, one plane buffer, fc weight hi in LDS)
+// the same for C = 96, hidden = 384 (4 x 4 tiles, one plane buffer, fc weight hi in LDS):
+// ffn_dwfc2_tb for fp32 h1 and tensors below 2 GiB, else ffn_dwfc2_kernel; sets ZS
 int launch_ffn_dwfc2(const DwFcArgs& a, int prec, hipStream_t s);
+// three depthwise waves + one staging / fc wave per SIMD (ffn_dwfc2_tb.hip); ZS set by the caller
+int launch_ffn_dwfc2_tb(const DwFcArgs& a, int prec, hipStream_t s);
+// ffn_dwfc2_tb addresses x, out and one h1 plane through 32-bit buffer byte offsets
+inline bool ffn_dwfc2_tb_fits(const DwFcArgs& a) {
+  return (int64_t)a.B * a.D * a.H * a.W * 96 * 4 < ((int64_t)1 << 31) &&
+         ((int64_t)a.H * a.W + 8) * 384 * 4 < ((int64_t)1 << 31);
+}
+// HW_ID (hwreg 4) bits [5:4]: the SIMD the wave runs on
+__device__ __forceinline__ int tb_simd_id() {
+  return (int)((__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4)) & 3);
+}
+// ---- diagnostic builds only (-DWF_DWFC2_PROBE; ffn_dwfc_sb, ffn_dwfc2 and ffn_dwfc2_tb):
+// per-wave cycles of workgroup 0 by phase between the kernel's barriers, 8 slots per wave
+#ifdef WF_DWFC2_PROBE
+#define PROBE_DECL                                                              \
+  const bool probe_on = blockIdx.x == 0;                                         \
+  long long pr_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pr_last = __builtin_amdgcn_s_memtime();
+#define PROBE(i)                                                                \
+  if (probe_on) {                                                               \
+    const long long t_ = __builtin_amdgcn_s_memtime();                          \
+    pr_acc[i] += t_ - pr_last;                                                  \
+    pr_last = t_;                                                               \
+  }
+#define PROBE_DUMP_TO(arr)                                                      \
+  if (probe_on && (tid & 63) == 0)                                              \
+    for (int i_ = 0; i_ < 8; ++i_) arr[wid * 8 + i_] = pr_acc[i_];
+#else
+#define PROBE_DECL
+#define PROBE(i)
+#define PROBE_DUMP_TO(arr)
+#endif
 // ---- the whole CCF_FFN + norm2 + Q4 residual in one kernel for C = 48, hidden = 192: the
 // haloed h1 plane is computed in LDS from the x rows (pw MFMA + LN1 + GELU), never stored
 int launch_ffn_fused(const DwFcArgs& a, int prec, hipStream_t s);
