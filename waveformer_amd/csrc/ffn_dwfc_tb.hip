@@ -18,12 +18,13 @@
 //   D waves (12 = 3 per SIMD): lane = (channel c, column pair cp = the SIMD): the 27 taps of
 //        channel c in VGPRs, per input row 4 ds_read_b32 (consecutive lanes = consecutive
 //        channels: conflict-free) feed 2 columns x up to 3 output rows x 3 output planes;
-//   E waves (4 = 1 per SIMD, s_setprio 3): the haloed 6 x 10 x 192 h1 plane staged by
-//        LDS-DMA (buffer_load_dwordx4 ... lds through a per-plane buffer descriptor, one plane
-//        ahead; out-of-volume positions and planes come back as zeros), the fc of one
-//        16-channel output column tile (waves 0..2) over the 32 positions on
+//   E waves (4 = 1 per SIMD, s_setprio 3):
+//        E0..E2: the fc of one 16-channel output column tile each over the 32 positions on
 //        v_mfma_f32_16x16x32 (x3 for bf16x3; weight hi in VGPRs, lo in LDS in fragment order),
-//        bias + Q4 residual + 16-B stores.
+//        bias + Q4 residual + 16-B stores;
+//        E3 (no fc tile): the loader -- the haloed 6 x 10 x 192 h1 plane staged by LDS-DMA
+//        (buffer_load_dwordx4 ... lds through a per-plane buffer descriptor, up to two planes
+//        ahead; out-of-volume positions and planes come back as zeros).
 // Staging on the D waves through registers cost them 800-1400 cycles of a ~5600-cycle plane
 // and needed 112 VGPRs; on the E waves by registers it needed > 128 VGPRs (spills).  LDS-DMA
 // needs neither.  fp32 h1 only (bf16x3, fp16 modes); the bf16 mode keeps ffn_dwfc_sb.
@@ -31,21 +32,45 @@
 // The tile leaves room for only two h2 tiles, so two barriers per plane as in ffn_dwfc_sb:
 //   phase 1: D slots 0, 1: LN2 of h2 tile (p-2), 16 lanes x 12 channels per position, 4
 //            positions per wave (8 per SIMD); D slot 2: scatter rows [0, S2) of plane p
-//            E: LDS-DMA of plane p+1 into the buffer plane p-1 left; residual rows of p-2
+//            E0..E2: fc of tile (p-3) + epilogue + store; residual rows of p-2
+//            E3: LDS-DMA pieces [FA, 45) of plane p+1 into the buffer plane p-1 left
 //   phase 2: D slots 0, 1: scatter rows [0, 6); slot 2: rows [S2, 6); all D: h2 tile p-1
-//            E: fc of tile (p-2) + epilogue + store; wait for the DMA
-// LDS: 2 x 46 KB planes + 2 x 25 KB h2 tiles + 18 KB fc lo fragments + vectors = 162,880 B.
-// (The 3 x 8 one-barrier predecessor and the first E-wave memory pipeline are in git history.)
+//            E3: LDS-DMA pieces [0, FA) of plane p+2 into the buffer plane p left; wait for
+//            plane p+1 (vmcnt(FA))
+// The phase probe (tools/tb4_phase_times.py, -DWF_DWFC2_PROBE) decides this placement: the
+// depthwise waves bound both phases (LN2 of slot 1 in phase 1, the scatter in phase 2), never
+// the plane fill, and whatever else runs on a SIMD beside them in phase 2 lengthens it.  So the
+// fc runs half an iteration late, in phase 1, where the E waves used to wait for the LN2, slot
+// 2 scatters its whole plane there (S2 = 6) beside the two LN2 waves, and the loader's pieces
+// go out in both phases without any wave waiting for them in the iteration of their issue.
+// LDS: 2 x 46,080 B planes + 2 x 25,600 B h2 tiles + 18,432 B fc lo fragments + 1,920 B
+// vectors = 163,712 B (+ 16 B of role counters).
+// (The 3 x 8 one-barrier predecessor, the first E-wave memory pipeline and the round-4..8
+// schedule -- every E wave staging a quarter plane in phase 1, fc in phase 2 -- are in git
+// history.)
 #include "kernels.hpp"
 
 namespace wf {
+
+#ifdef WF_DWFC2_PROBE
+// diagnostic builds only: per-wave cycles of workgroup 0 by phase (tools/tb4_phase_times.py):
+// slot 0 phase-1 work (E: residual loads), 1 wait at barrier 1, 2 phase-2 work (E: fc + stores),
+// 3 wait at barrier 2, 4 DMA issue, 5 the DMA wait (vmcnt) that ends phase 2, 6 role, 7 iterations
+__device__ long long g_dwfctb4_probe[16 * 8];
+extern "C" int wf_debug_dwfctb4_probe(long long* host) {
+  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_dwfctb4_probe), sizeof(g_dwfctb4_probe));
+}
+#endif
 
 #ifndef WF_TB_EPRIO
 #define WF_TB_EPRIO 3
 #endif
 
 namespace tb4 {
-constexpr int S2 = 4;  // input rows the third D wave of a SIMD scatters in phase 1
+#ifndef WF_TB4_S2
+#define WF_TB4_S2 6
+#endif
+constexpr int S2 = WF_TB4_S2;  // input rows the third D wave of a SIMD scatters in phase 1
 constexpr int C = 48, HID = 192, TY = 4, TX = 8;
 constexpr int PY = TY + 2, PX = TX + 2, PP = PY * PX;  // 6 x 10
 constexpr int NPOS = TY * TX;                          // 32
@@ -60,7 +85,13 @@ constexpr int PLANE_F = PP * HID;
 constexpr int H2F = NPOS * HS;
 constexpr int NV = HID / 4;
 constexpr int NPC = (PP * NV + 63) / 64;               // 45 LDS-DMA pieces
-constexpr int NPCE = (NPC + 3) / 4;
+static_assert(NPC * 64 == PP * NV, "whole pieces only: the loader issues no partial piece");
+// pieces of a plane the loader issues half an iteration early (part A, see the loader)
+#ifndef WF_TB4_FA
+#define WF_TB4_FA 16
+#endif
+constexpr int FA = WF_TB4_FA;
+static_assert(FA >= 0 && NPC + FA <= 63, "outstanding pieces must fit the 6-bit vmcnt");
 constexpr int KS = HID / 32;
 constexpr int FWL_BYTES = (C / 16) * KS * 64 * 16;
 // vectors: LN2 affine (HID each), fc bias + norm2 bias folded into one (C), norm2 weight (C)
@@ -128,6 +159,11 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc_tb4_kernel(DwFcArgs a) {
   const bool even = simd_cnt[0] == 4 && simd_cnt[1] == 4 && simd_cnt[2] == 4 && simd_cnt[3] == 4;
   int role = even ? (slot < 3 ? 3 * simd + slot : 12 + simd) : wid;
   role = __builtin_amdgcn_readfirstlane(role);
+  PROBE_DECL
+#ifdef WF_DWFC2_PROBE
+  pr_acc[6] = role;
+  pr_acc[7] = z1 + 3 - z0;
+#endif
 
   if (role < 12) {
     // ================================ D waves ===========================================
@@ -238,7 +274,9 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc_tb4_kernel(DwFcArgs a) {
         load_plane();
         rows(vin, SA(), SB(), SC(), I0(), IS());
       }
+      PROBE(0)
       __syncthreads();  // 1 -> 2: LN2'd tile (p-2) visible to the fc
+      PROBE(1)
       // ---- phase 2
       if (live) {
         if (kslot < 2) rows(vin, SA(), SB(), SC(), I0(), IP());
@@ -252,22 +290,108 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc_tb4_kernel(DwFcArgs a) {
               h2t[(o * TX + 2 * cp + j) * HS + c] = acc[R][o][j] + bias;
         }
       }
+      PROBE(2)
       __syncthreads();  // 2 -> next 1
+      PROBE(3)
     };
     for (int p = z0 - 1; p <= z1 + 1; p += 3) {
       step(p, std::integral_constant<int, 0>());
       if (p + 1 <= z1 + 1) step(p + 1, std::integral_constant<int, 1>());
       if (p + 2 <= z1 + 1) step(p + 2, std::integral_constant<int, 2>());
     }
+    PROBE_DUMP_TO(g_dwfctb4_probe)
     return;
   }
 
   // ================================== E waves ============================================
-  __builtin_amdgcn_s_setprio(WF_TB_EPRIO);
   const int e = role - 12;
+  if (e == C / 16) {
+    __builtin_amdgcn_s_setprio(3);
+    // ============================ E3: the plane loader ====================================
+    // The fourth E wave has no fc tile, no residual loads and no stores: its VM queue holds
+    // LDS-DMA pieces only, in issue order, so a counted vmcnt on it is exact.  It stages every
+    // plane alone, 45 pieces of 1 KiB, split in two parts that go out in different phases:
+    //   part A = pieces [0, FA) of plane p + 2 in phase 2 of iteration p,
+    //   part B = pieces [FA, 45) of plane p + 1 in phase 1 of iteration p,
+    // so pieces are in flight through both phases and the wait that ends phase 2, vmcnt(FA),
+    // retires plane p + 1 (everything older than part A of p + 2) without draining the queue.
+    // * Buffer reuse: plane q lives in buffer (q - z0 + 1) & 1.  Every D wave reads plane p out
+    //   into registers in phase 1 of iteration p, and its barrier 1 (__syncthreads: lgkmcnt(0)
+    //   first) follows those reads.  Part A of p + 2 (the buffer of p) is issued after barrier 1
+    //   of iteration p; part B of p + 1 (the buffer of p - 1) after barrier 2 of iteration p - 1,
+    //   i.e. after barrier 1 of iteration p - 1.  The prologue's pieces follow the barrier behind
+    //   the weight reads (the weights lie in buffer 0).
+    // * Visibility: plane p + 1 is read in phase 1 of iteration p + 1, behind barrier 2 of
+    //   iteration p, which this wave enters only after vmcnt(FA) (vmcnt(0) when no part A was
+    //   issued) has retired every piece of plane p + 1.  Wait, barrier, read: one barrier between
+    //   the covering wait and the first ds_read, as before.  The barriers here are bare
+    //   s_barriers: __syncthreads()' fence would drain the pieces left in flight.
+    // * Segments: planes z0 - 1 .. z1 are staged (ZS + 2 >= 3 of them), every iteration
+    //   p = z0 - 1 .. z1 + 1 tests p + 1 <= z1 and p + 2 <= z1 itself, so a segment of any length
+    //   (the last, ragged one included) takes this one loop; no piece beyond 45 per plane, no
+    //   padding.  Out-of-volume planes go through a zero-size descriptor and out-of-volume
+    //   positions through offset 0x80000000: both land as zeros.
+    // * At most 45 + FA pieces are outstanding (a whole plane and the next one's part A), within
+    //   the 6-bit vmcnt.
+    const float* src = reinterpret_cast<const float*>(a.h1) + (int64_t)b * D * H * W * HID;
+    const int64_t plane_elems = (int64_t)H * W * HID;
+    // the pieces' source offsets within a plane, once per tile (this wave has the registers)
+    uint32_t off[NPC];
+#pragma unroll
+    for (int j = 0; j < NPC; ++j) {
+      const int i = j * 64 + lane;
+      const int pos = i / NV, v = i - pos * NV;
+      const int yy = y0 - 1 + pos / PX, xx = x0 - 1 + pos % PX;
+      const bool ok = yy >= 0 && yy < H && xx >= 0 && xx < W;
+      off[j] = ok ? (uint32_t)(((yy * W + xx) * HID + 4 * v) * 4) : 0x80000000u;
+    }
+    auto fill = [&](int p, auto LOc, auto HIc) {
+      constexpr int LO = decltype(LOc)::value, HI = decltype(HIc)::value;
+      float* dst = planes + ((p - z0 + 1) & 1) * PLANE_F;
+      const bool pz = p >= 0 && p < D;
+      const float* base = src + (int64_t)min(max(p, 0), D - 1) * plane_elems;
+      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+          const_cast<float*>(base), 0, pz ? (int)(plane_elems * 4) : 0, 0x00020000);
+#pragma unroll
+      for (int j = LO; j < HI; ++j)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(
+            rs, (__attribute__((address_space(3))) void*)(dst + j * 256), 16, off[j], 0, 0, 0);
+    };
+    typedef std::integral_constant<int, 0> F0;
+    typedef std::integral_constant<int, FA> FAc;
+    typedef std::integral_constant<int, NPC> FN;
+    const bool fetch = !(ffn_dbg(a) & 8);
+    __syncthreads();  // (prologue) weights read out of the plane buffer
+    fill(z0 - 1, F0(), FN());
+    fill(z0, F0(), FAc());
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(FA) : "memory");
+    __builtin_amdgcn_s_barrier();  // (prologue) plane z0-1 staged
+    for (int p = z0 - 1; p <= z1 + 1; ++p) {
+      // ---- phase 1: the rest of plane p + 1
+      if (p + 1 <= z1 && fetch) fill(p + 1, FAc(), FN());
+      PROBE(4)
+      __builtin_amdgcn_s_barrier();  // 1 -> 2: every D wave holds plane p in registers
+      PROBE(1)
+      // ---- phase 2: the head of plane p + 2 into the buffer plane p just left, then the wait
+      // for plane p + 1
+      if (p + 2 <= z1 && fetch) {
+        fill(p + 2, F0(), FAc());
+        PROBE(2)
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(FA) : "memory");
+      } else {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
+      PROBE(5)
+      __builtin_amdgcn_s_barrier();  // 2 -> next 1
+      PROBE(3)
+    }
+    PROBE_DUMP_TO(g_dwfctb4_probe)
+    return;
+  }
+  // =============================== E0..E2: the fc waves ===================================
+  __builtin_amdgcn_s_setprio(WF_TB_EPRIO);
   const int l15 = lane & 15, g4 = lane >> 4;
-  const bool has_fc = e < C / 16;
-  const int ct = has_fc ? e : 0;
+  const int ct = e;
   const float bs = a.bscale ? a.bscale[b] : 1.f;
   bf16x8 fwh[KS];
   {
@@ -276,31 +400,6 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc_tb4_kernel(DwFcArgs a) {
     for (int ks = 0; ks < KS; ++ks) fwh[ks] = *reinterpret_cast<const bf16x8*>(wr + ks * 32);
   }
   const bf16x8* fwl = fwlo + ct * KS * 64 + lane;
-  const float* src = reinterpret_cast<const float*>(a.h1) + (int64_t)b * D * H * W * HID;
-  const int64_t plane_elems = (int64_t)H * W * HID;
-  // the DMA pieces' source offsets (k-th piece of this E wave), recomputed per plane -- the E
-  // waves have VALU to spare and the registers went to the residual sets
-  auto piece_off = [&](int k) {
-    const int i = min((4 * k + e) * 64 + lane, PP * NV - 1);
-    const int pos = i / NV, v = i - pos * NV;
-    const int yy = y0 - 1 + pos / PX, xx = x0 - 1 + pos % PX;
-    const bool ok = yy >= 0 && yy < H && xx >= 0 && xx < W;
-    return ok ? (uint32_t)(((yy * W + xx) * HID + 4 * v) * 4) : 0x80000000u;
-  };
-  auto stage = [&](int p, float* dst) {
-    const bool pz = p >= 0 && p < D;
-    const float* base = src + (int64_t)min(max(p, 0), D - 1) * plane_elems;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(base), 0, pz ? (int)(plane_elems * 4) : 0, 0x00020000);
-#pragma unroll
-    for (int k = 0; k < NPCE; ++k) {
-      const int j = 4 * k + e;
-      const uint32_t o = piece_off(k);
-      if (j * 64 < PP * NV && (j * 64 + lane < PP * NV))
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            rs, (__attribute__((address_space(3))) void*)(dst + j * 256), 16, o, 0, 0, 0);
-    }
-  };
   const int col = ct * 16 + 4 * g4;
   const float* sbase = a.stats ? a.stats : a.x;
   auto gpos_of = [&](int zo, int rt, bool clamp) {
@@ -316,16 +415,15 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc_tb4_kernel(DwFcArgs a) {
     const int lp = rt * 16 + l15;
     return y0 + lp / TX < H && x0 + lp % TX < W;
   };
-  // The E waves' memory pipeline (vmcnt retires in issue order and counts stores too):
-  //   * the residual rows of output plane zo + 1 are loaded in iteration p (ahead of the plane
-  //     DMA), into the register set of zo + 1's parity, and used by the fc one iteration later
-  //     -- the fc never waits for a load younger than the DMA, i.e. never for the DMA itself;
+  // The fc waves' memory pipeline:
+  //   * the residual rows of output plane zo + 1 are loaded in iteration p, into the register
+  //     set of zo + 1's parity, and used by the fc one iteration later: the fc does not wait
+  //     for a memory round trip;
   //   * the output rows go out as range-checked buffer stores (rows outside the volume get an
-  //     out-of-range offset and are dropped), exactly two per fc wave, so the end-of-phase wait
-  //     for the DMA is vmcnt(2): it no longer waits for the stores to reach memory.
-  // The first version loaded the residual in the same iteration, behind the
-  // DMA, so the fc waited for both, and drained vmcnt(0) over its stores: two memory round
-  // trips per plane on the E wave's path to the barrier.
+  //     out-of-range offset and are dropped) and are never waited for.
+  // These waves issue no LDS-DMA (the loader above does), so nothing of theirs has to land
+  // before a barrier.  (Until round 9 every E wave staged a quarter of the plane in phase 1 and
+  // ended phase 2 on vmcnt(2), the wait for its pieces; that version is in git history.)
   // residual / statistics rows through 32-bit buffer offsets (64-bit pointer pairs for the two
   // register sets spilled: the host keeps the tensors under 2 GiB)
   f32x4 xr[2][2];
@@ -373,43 +471,48 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc_tb4_kernel(DwFcArgs a) {
   };
 
   __syncthreads();  // (prologue) weights read out of the plane buffer
-  stage(z0 - 1, planes);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();  // (prologue) plane z0-1 staged
-  // iteration p: zo = p - 2; register set of output plane z: (z - z0) & 1, a compile-time S
-  // for the fc (zo) and S ^ 1 for the prefetch (zo + 1) with the loop unrolled by two
-  auto iter = [&](int p, auto Sc) {
+  // iteration p: the fc of tile zo = p - 3 in PHASE 1, half an iteration after the phase 2 in
+  // which it could first run.  Tile zo was LN2'd in phase 1 of iteration p - 1 and its buffer is
+  // next written (h2 tile zo + 2) in phase 2 of iteration p, behind barrier 1, which this wave
+  // enters with its LDS reads complete (lgkmcnt(0)); phase 1's LN2 works on the other buffer.
+  // Register set of output plane z: (z - z0) & 1, a compile-time S for the fc (zo) and S ^ 1
+  // for the prefetch (zo + 1, used one iteration later) with the loop unrolled by two.
+  auto fc_tile = [&](int zo, auto Sc) {
     constexpr int S = decltype(Sc)::value;
-    const int zo = p - 2;
-    const bool epi = has_fc && zo >= z0 && zo < z1;
-    // ---- phase 1: residual rows of zo + 1, then plane p + 1 into the buffer p - 1 left
-    if (has_fc && zo + 1 >= z0 && zo + 1 < z1) load_resid(zo + 1, xr[S ^ 1], es[S ^ 1]);
-    if (p + 1 <= z1 && !(ffn_dbg(a) & 8)) stage(p + 1, planes + ((p + 2 - z0) & 1) * PLANE_F);
-    // 1 -> 2 as a bare s_barrier: __syncthreads()' workgroup release fence makes the compiler
-    // drain vmcnt(0) first -- the LDS-DMA writes LDS, so the fence waited for the plane just
-    // issued and put a full memory round trip in front of every plane's phase 2.  This wave
-    // wrote no LDS in phase 1; the DMA is waited for at the end of phase 2.
-    __builtin_amdgcn_s_barrier();
-    // ---- phase 2: fc of tile zo + epilogue; the staged plane must land before the barrier,
-    // the two stores may still be in flight
-    if (epi && !(ffn_dbg(a) & 4)) {
+    if (zo >= z0 && zo < z1 && !(ffn_dbg(a) & 4)) {
       const float* h2t = h2b + ((zo - z0) & 1) * H2F;
       fc_store(h2t, zo, 0, xr[S][0], es[S][0]);
       fc_store(h2t, zo, 1, xr[S][1], es[S][1]);
-      asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    // bare as well (its fence would drain the stores): the DMA has landed (waited above) and
-    // the LDS reads of the fc are complete before the barrier (lgkmcnt)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();  // 2 -> next 1
   };
-  // (zo - z0) & 1 at p = z0 - 1 + i is (i + 1) & 1: even i -> S = 1
+  auto iter = [&](int p, auto Sc) {
+    constexpr int S = decltype(Sc)::value;
+    const int zo = p - 3;
+    // ---- phase 1: fc of tile zo + epilogue (the two stores stay in flight), then the residual
+    // rows of zo + 1
+    fc_tile(zo, Sc);
+    PROBE(2)
+    if (zo + 1 >= z0 && zo + 1 < z1) load_resid(zo + 1, xr[S ^ 1], es[S ^ 1]);
+    PROBE(0)
+    // bare s_barriers: __syncthreads()' workgroup release fence would drain vmcnt(0), i.e. the
+    // stores and the residual rows just requested.  This wave writes no LDS.
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();  // 1 -> 2
+    PROBE(1)
+    // ---- phase 2: nothing
+    __builtin_amdgcn_s_barrier();  // 2 -> next 1
+    PROBE(3)
+  };
+  // (zo - z0) & 1 at p = z0 - 1 + i is i & 1: even i -> S = 0
   for (int p = z0 - 1; p <= z1 + 1; p += 2) {
-    iter(p, std::integral_constant<int, 1>());
-    if (p + 1 <= z1 + 1) iter(p + 1, std::integral_constant<int, 0>());
+    iter(p, std::integral_constant<int, 0>());
+    if (p + 1 <= z1 + 1) iter(p + 1, std::integral_constant<int, 1>());
   }
+  // the last tile, z1 - 1 (LN2'd in phase 1 of the last iteration), behind the last barrier
+  if ((z1 - 1 - z0) & 1) fc_tile(z1 - 1, std::integral_constant<int, 1>());
+  else fc_tile(z1 - 1, std::integral_constant<int, 0>());
+  PROBE_DUMP_TO(g_dwfctb4_probe)
 }
 
 int launch_ffn_dwfc_tb4(const DwFcArgs& a, int prec, hipStream_t s) {
