@@ -410,6 +410,38 @@ def test_ccf_ffn_stage1_batch_beyond_tb4_range():
     del x, out
 
 
+def test_ccf_ffn_stage1_plane_beyond_tb4_range():
+    """ffn_dwfc_tb4 addresses one h1 plane through 32-bit byte offsets and marks halo positions
+    outside the volume with offset 2^31, which must lie beyond the plane: a plane of
+    H * W * 192 * 4 >= 2^31 bytes has to take the unlimited kernel (with tb4 its border halos
+    would read real data instead of the zero padding).  1673^2 is the smallest square over the
+    limit, ragged in both directions.  Reference: the same op on the top and bottom crops of
+    841 rows (planes under the limit: tb4); with D = 1 and the pointwise front half, rows
+    [0, 840) of a crop see exactly what they see in the whole plane."""
+    import waveformer_amd.network_models as NM
+    from oracle.weight_rule import rule_state_dict
+    from waveformer_amd import ops
+    S, K = 1673, 841
+    assert S * S * 192 * 4 >= 2 ** 31 > (S - 1) * (S - 1) * 192 * 4 and K * S * 192 * 4 < 2 ** 31
+    mlp = NM.CCF_FFN(48, 192, img_size=(1, S, S))
+    mlp.load_state_dict(rule_state_dict(mlp.state_dict()))
+    mlp = mlp.eval().to(DEV)
+    with torch.no_grad(), ops.precision("bf16x3"):
+        x = torch.randn((1, 1, S, S, 48), device=DEV, generator=torch.Generator(DEV).manual_seed(7))
+        out = ops.ccf_ffn(x, None, None, mlp, None)
+        top = ops.ccf_ffn(x[:, :, :K].contiguous(), None, None, mlp, None)
+        bot = ops.ccf_ffn(x[:, :, S - K:].contiguous(), None, None, mlp, None)
+    torch.cuda.synchronize()
+    def rel_l2(a, b):  # C.rel_l2 without the 2 x 540 MB trip to the host
+        return ((a.double() - b.double()).norm() / (b.double().norm() + 1e-30)).item()
+
+    e_top = rel_l2(out[:, :, :K - 1], top[:, :, :K - 1])
+    e_bot = rel_l2(out[:, :, S - K + 1:], bot[:, :, 1:])
+    print(f"plane beyond tb4 range: rel_l2 top {e_top:.3e} bottom {e_bot:.3e}")
+    assert e_top <= 1e-6 and e_bot <= 1e-6
+    del x, out, top, bot
+
+
 @pytest.mark.parametrize("shape", [(2, 8, 8, 8), (1, 5, 6, 11), (3, 7, 4, 9), (1, 20, 8, 8),
                                    (1, 16, 16, 16)])
 @pytest.mark.parametrize("block", [False, True])

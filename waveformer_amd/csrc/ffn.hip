@@ -537,6 +537,35 @@ int launch_dwconv_ln_gelu(const void* in, const float* w, const float* b, const 
   return check_launch("dwconv_ln_gelu");
 }
 
+// the back half's argument block (ZS and dbg are the launchers'; the whole-FFN kernel's front
+// half is added by its caller)
+static DwFcArgs dwfc_args(const void* h1, const float* dw_w, const float* dw_b, const float* ln2_w,
+                          const float* ln2_b, float eps2, const uint16_t* fc, const float* fc_b,
+                          const float* x, const float* stats, const float* n2_w,
+                          const float* n2_b, const float* bscale, float* out, int64_t B, int64_t D,
+                          int64_t H, int64_t W) {
+  DwFcArgs d{};
+  d.h1 = h1;
+  d.dw_w = dw_w;
+  d.dw_b = dw_b;
+  d.ln2_w = ln2_w;
+  d.ln2_b = ln2_b;
+  d.eps2 = eps2;
+  d.fc = fc;
+  d.fc_b = fc_b;
+  d.x = x;
+  d.stats = stats;
+  d.n2_w = n2_w;
+  d.n2_b = n2_b;
+  d.bscale = bscale;
+  d.out = out;
+  d.B = (int)B;
+  d.D = (int)D;
+  d.H = (int)H;
+  d.W = (int)W;
+  return d;
+}
+
 }  // namespace wf
 
 using namespace wf;
@@ -634,24 +663,8 @@ extern "C" int wf_ccf_ffn_stage(int stage, const float* xh, const float* stats,
   const bool whole = getenv("WF_FFN_FUSED") != nullptr;  // per call: tests switch it
   if (!keep && whole && C == 48 && hidden == 192) {
     if (stage == 1 || stage == 3) return 0;
-    DwFcArgs d{};
-    d.dw_w = dw_w;
-    d.dw_b = dw_b;
-    d.ln2_w = ln2_w;
-    d.ln2_b = ln2_b;
-    d.eps2 = eps2;
-    d.fc = fc_bf16x2;
-    d.fc_b = fc_b;
-    d.x = xh;
-    d.stats = stats;
-    d.n2_w = n2_w;
-    d.n2_b = n2_b;
-    d.bscale = branch_scale;
-    d.out = out;
-    d.B = (int)B;
-    d.D = (int)D;
-    d.H = (int)H;
-    d.W = (int)W;
+    DwFcArgs d = dwfc_args(nullptr, dw_w, dw_b, ln2_w, ln2_b, eps2, fc_bf16x2, fc_b, xh, stats, n2_w,
+                           n2_b, branch_scale, out, B, D, H, W);
     d.pw = pw_bf16x2;
     d.pw_b = pw_b;
     d.ln1_w = ln1_w;
@@ -706,25 +719,8 @@ extern "C" int wf_ccf_ffn_stage(int stage, const float* xh, const float* stats,
   const bool dwfc1 = C == 48 && hidden == 192, dwfc2 = C == 96 && hidden == 384;
   if (!keep && !no_dwfc && (dwfc1 || dwfc2)) {
     if (stage == 1 || stage == 3) return rc;  // stage 3 (fc) is part of the fused kernel
-    DwFcArgs d{};
-    d.h1 = h1;
-    d.dw_w = dw_w;
-    d.dw_b = dw_b;
-    d.ln2_w = ln2_w;
-    d.ln2_b = ln2_b;
-    d.eps2 = eps2;
-    d.fc = fc_bf16x2;
-    d.fc_b = fc_b;
-    d.x = xh;
-    d.stats = stats;
-    d.n2_w = n2_w;
-    d.n2_b = n2_b;
-    d.bscale = branch_scale;
-    d.out = out;
-    d.B = (int)B;
-    d.D = (int)D;
-    d.H = (int)H;
-    d.W = (int)W;
+    const DwFcArgs d = dwfc_args(h1, dw_w, dw_b, ln2_w, ln2_b, eps2, fc_bf16x2, fc_b, xh, stats,
+                                 n2_w, n2_b, branch_scale, out, B, D, H, W);
     return dwfc1 ? launch_ffn_dwfc_s1(d, precision, s) : launch_ffn_dwfc2(d, precision, s);
   }
   const bool split_ln = hidden % 32 == 0;

@@ -17,7 +17,7 @@
 // (ffn_dwfc_tb.hip); ffn_dwfc_sb below serves PREC_BF16 and outputs of 2 GiB and above.
 // Likewise for the stage-2 shape (C = 96, hidden = 384): the default is ffn_dwfc2_tb
 // (ffn_dwfc2_tb.hip); ffn_dwfc2_kernel below serves PREC_BF16 and tensors of 2 GiB and above.
-#include "kernels.hpp"
+#include "ffn_dwfc_common.hpp"
 
 namespace wf {
 
@@ -82,11 +82,6 @@ extern "C" int wf_debug_dwfc2_probe(long long* host) {
 // of DESIGN.md 6.1 could not apply) measured 1058-1066 us: v_pk_fma_f32 costs the issue time
 // of two v_fma_f32 here, so it is not used.
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ int hw_simd_id() {
-  // HW_ID (hwreg 4) bits [5:4]: the SIMD the wave runs on
-  return (int)((__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4)) & 3);
-}
-
 template <int P, typename T>
 __global__ __launch_bounds__(768, 1) void ffn_dwfc_sb_kernel(DwFcArgs a) {
   constexpr int C = 48, HID = 192, TY = 4, TX = 8;
@@ -113,29 +108,13 @@ __global__ __launch_bounds__(768, 1) void ffn_dwfc_sb_kernel(DwFcArgs a) {
   const int tid = threadIdx.x;
   const int wid = tid >> 6, lane = tid & 63;
   const int D = a.D, H = a.H, W = a.W;
-  const int ntx = (W + TX - 1) / TX, nty = (H + TY - 1) / TY, nzs = (D + a.ZS - 1) / a.ZS;
-  const int nb = gridDim.x;
-  const int xcd = blockIdx.x & 7, q8 = nb >> 3, r8 = nb & 7;
-  int t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
-  const int xt = t % ntx;
-  t /= ntx;
-  const int yt = t % nty;
-  t /= nty;
-  const int zt = t % nzs;
-  const int b = t / nzs;
-  const int x0 = xt * TX, y0 = yt * TY, z0 = zt * a.ZS, z1 = min(z0 + a.ZS, D);
+  const DwFcTile tl = dwfc_tile<TY, TX>(a);
+  const int b = tl.b, x0 = tl.x0, y0 = tl.y0, z0 = tl.z0, z1 = tl.z1;
   const int64_t plane_sz = (int64_t)H * W;
 
   if (tid < 4) simd_cnt[tid] = 0;
-  for (int i = tid; i < HID; i += K::NTH) {
-    lnw[i] = 0.5f * a.ln2_w[i];
-    lnb[i] = 0.5f * a.ln2_b[i];
-  }
-  for (int i = tid; i < C; i += K::NTH) {
-    fcb[i] = a.fc_b ? a.fc_b[i] : 0.f;
-    n2w[i] = a.stats ? a.n2_w[i] : 1.f;
-    n2b[i] = a.stats ? a.n2_b[i] : 0.f;
-  }
+  dwfc_stage_ln2<HID>(lnw, lnb, a, K::NTH);
+  dwfc_stage_epi<C>(fcb, n2w, n2b, a, K::NTH);
   if (SPLIT)
     for (int i = tid; i < C * HID / 8; i += K::NTH)
       reinterpret_cast<bf16x8*>(fwlo)[i] = reinterpret_cast<const bf16x8*>(a.fc + C * HID)[i];
@@ -144,66 +123,15 @@ __global__ __launch_bounds__(768, 1) void ffn_dwfc_sb_kernel(DwFcArgs a) {
   for (int i = tid; i < HID; i += K::NTH) planes[HID * 27 + i] = a.dw_b[i];
   __syncthreads();
   // ---- roles: per SIMD, arrival slots 0, 1 -> D waves 2 s, 2 s + 1; slot 2 -> E wave s
-  const int simd = hw_simd_id();
-  int slot = 0;
-  if (lane == 0) slot = atomicAdd(&simd_cnt[simd], 1);
-  slot = __builtin_amdgcn_readfirstlane(__shfl(slot, 0, 64));
-  __syncthreads();
-  const bool even = simd_cnt[0] == 3 && simd_cnt[1] == 3 && simd_cnt[2] == 3 && simd_cnt[3] == 3;
-  int role = even ? (slot < 2 ? 2 * simd + slot : 8 + simd) : wid;  // 0..7 D, 8..11 E
-  role = __builtin_amdgcn_readfirstlane(role);
-
-  // LN2 + GELU + the bf16 hi / lo split of one h2 tile row, rewritten in place (16 lanes)
-  auto ln2_row = [&](float* h2t, int pos, int g) {
-    float* row = h2t + pos * K::HS;
-    float v[LNC];
-#pragma unroll
-    for (int j = 0; j < LNC / 4; ++j) {
-      const f32x4 u = *reinterpret_cast<const f32x4*>(row + g * LNC + 4 * j);
-      v[4 * j] = u.x;
-      v[4 * j + 1] = u.y;
-      v[4 * j + 2] = u.z;
-      v[4 * j + 3] = u.w;
-    }
-    // short dependency chains: three-way column sums (depth 3 + 2 instead of 12), four
-    // variance partials, the raw v_rsq_f32 (var + eps >= eps is a normal number)
-    float s4[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) s4[j] = (v[j] + v[j + 4]) + v[j + 8];
-    const float mean = group_sum<LNL>((s4[0] + s4[1]) + (s4[2] + s4[3])) * (1.f / HID);
-    float q4[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float d0 = v[j] - mean, d1 = v[j + 4] - mean, d2 = v[j + 8] - mean;
-      q4[j] = d2 * d2 + (d1 * d1 + d0 * d0);
-    }
-    const float rstd = __builtin_amdgcn_rsqf(
-        group_sum<LNL>((q4[0] + q4[1]) + (q4[2] + q4[3])) * (1.f / HID) + a.eps2);
-    const float nmr = -mean * rstd;
-    uint16_t* rowh = reinterpret_cast<uint16_t*>(row);
-#pragma unroll
-    for (int j = 0; j < LNC / 4; ++j) {
-      const int c = g * LNC + 4 * j;
-      const f32x4 lw4 = *reinterpret_cast<const f32x4*>(lnw + c);
-      const f32x4 lb4 = *reinterpret_cast<const f32x4*>(lnb + c);
-      const f32x4 y = gelu_half4((f32x4{v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]} *
-                                  rstd + nmr) * lw4 + lb4);
-      bf16x4 hi4, lo4;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const uint16_t hb = op_cvt<P>(y[k]);
-        hi4[k] = (short)hb;
-        lo4[k] = op_lo<P>(y[k], hb);
-      }
-      *reinterpret_cast<bf16x4*>(rowh + c) = hi4;
-      if (SPLIT) *reinterpret_cast<bf16x4*>(rowh + HID + c) = lo4;
-    }
-  };
+  const int role = dwfc_wave_role<3>(simd_cnt, wid, lane);  // 0..7 D, 8..11 E
 
   PROBE_DECL
 #ifdef WF_DWFC2_PROBE
   pr_acc[6] = role;
-  pr_acc[7] = simd * 16 + slot + (even ? 256 : 0);
+  {  // SIMD, arrival slot and "every SIMD got three waves" (the slot is only known then)
+    const bool even = simd_cnt[0] == 3 && simd_cnt[1] == 3 && simd_cnt[2] == 3 && simd_cnt[3] == 3;
+    pr_acc[7] = tb_simd_id() * 16 + (even ? (role < 8 ? role & 1 : 2) + 256 : 0);
+  }
 #endif
   if (role < 8) {
     // ================================ D waves: depthwise scatter ==========================
@@ -289,7 +217,9 @@ __global__ __launch_bounds__(768, 1) void ffn_dwfc_sb_kernel(DwFcArgs a) {
       if (zl >= z0 && zl < z1 && !(ffn_dbg(a) & 2)) {
         int ltid = lane;
         asm volatile("" : "+v"(ltid));
-        ln2_row(h2b + ((zl - z0) & 1) * H2F, 4 * xc + ltid / LNL, ltid % LNL);
+        // position 4 xc + ltid / 16 of the tile, 12 contiguous channels per lane
+        float* row = h2b + ((zl - z0) & 1) * H2F + (4 * xc + ltid / LNL) * K::HS;
+        dwfc_ln2_row<P, HID, LNL, 4, true>(row, LNC * (ltid % LNL), lnw, lnb, a.eps2);
       }
       PROBE(0)
       __syncthreads();  // 1 -> 2
@@ -342,10 +272,13 @@ __global__ __launch_bounds__(768, 1) void ffn_dwfc_sb_kernel(DwFcArgs a) {
 #pragma unroll
     for (int ks = 0; ks < HID / 32; ++ks) fwh[ks] = *reinterpret_cast<const bf16x8*>(wr + ks * 32);
   }
-  // h1 staging: byte offsets inside one plane, loaded through a per-plane buffer descriptor
-  // (32-bit voffsets).  Halo positions outside the volume get an offset past the descriptor's
-  // range and planes outside [0, D) a zero-range descriptor: the loads return the zero
-  // padding themselves and the commit is a plain copy.
+  // h1 staging through a buffer descriptor over the tile's haloed rows [yb, ye) of one plane
+  // (at most PY rows of W positions: far below BUF_OOR whatever the plane's size, so this
+  // kernel has no 2 GiB limit), 32-bit byte voffsets from row yb.  Halo positions outside the
+  // volume get BUF_OOR and planes outside [0, D) a zero-range descriptor: the loads return the
+  // zero padding themselves and the commit is a plain copy.
+  const int yb = max(y0 - 1, 0), ye = min(y0 + TY + 1, H);
+  const int64_t row_elems = (int64_t)W * HID;
   uint32_t off[NLDE];
 #pragma unroll
   for (int j = 0; j < NLDE; ++j) {
@@ -353,14 +286,14 @@ __global__ __launch_bounds__(768, 1) void ffn_dwfc_sb_kernel(DwFcArgs a) {
     const int pos = i / K::NV, v = i - pos * K::NV;
     const int yy = y0 - 1 + pos / K::PX, xx = x0 - 1 + pos % K::PX;
     const bool ok = yy >= 0 && yy < H && xx >= 0 && xx < W;
-    off[j] = ok ? (uint32_t)(((yy * W + xx) * HID + 4 * v) * (int)sizeof(T)) : 0x80000000u;
+    off[j] = ok ? (uint32_t)((((yy - yb) * W + xx) * HID + 4 * v) * (int)sizeof(T)) : (uint32_t)BUF_OOR;
   }
   typename L::raw stg[NLDE];
   auto fetch = [&](int p) {
     const bool pz = p >= 0 && p < D;
-    const T* base = src + (int64_t)min(max(p, 0), D - 1) * plane_elems;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<T*>(base), 0, pz ? (int)(plane_elems * (int64_t)sizeof(T)) : 0, 0x00020000);
+    const T* base = src + (int64_t)min(max(p, 0), D - 1) * plane_elems + yb * row_elems;
+    const __amdgpu_buffer_rsrc_t rs =
+        buf_rsrc(base, pz ? (int)((ye - yb) * row_elems * (int64_t)sizeof(T)) : 0);
 #pragma unroll
     for (int j = 0; j < NLDE; ++j) {
       if constexpr (sizeof(T) == 4)
@@ -408,24 +341,10 @@ __global__ __launch_bounds__(768, 1) void ffn_dwfc_sb_kernel(DwFcArgs a) {
     for (int ks = 0; ks < HID / 32; ++ks) {
       const int k = ks * 32 + 8 * g4;
       const bf16x8 bh = *reinterpret_cast<const bf16x8*>(Bh + k);
-      if (SPLIT) {
-        const bf16x8 bl = *reinterpret_cast<const bf16x8*>(Bh + HID + k);
-        acc = mma32<P>(fwh[ks], bl, acc);
-        acc = mma32<P>(*reinterpret_cast<const bf16x8*>(fwl + ks * 32), bh, acc);
-      }
-      acc = mma32<P>(fwh[ks], bh, acc);
+      const bf16x8 bl = *reinterpret_cast<const bf16x8*>(Bh + HID + k);
+      acc = dwfc_mma3<P>(acc, fwh[ks], *reinterpret_cast<const bf16x8*>(fwl + ks * 32), bh, bl);
     }
-    f32x4 v = acc + *reinterpret_cast<const f32x4*>(fcb + col);
-    const f32x4 xv = xr[rt];
-    if (a.stats) {
-      const f32x4 lw = *reinterpret_cast<const f32x4*>(n2w + col);
-      const f32x4 lb = *reinterpret_cast<const f32x4*>(n2b + col);
-      const float em = es[rt].x, er = es[rt].y;
-      const f32x4 n2 = (xv - em) * er * lw + lb;
-      v = xv + (n2 + v) * bs;
-    } else {
-      v = xv + v * bs;
-    }
+    const f32x4 v = dwfc_epilogue(acc, fcb, n2w, n2b, col, xr[rt], es[rt], bs, a.stats != nullptr);
     if (row_ok(rt)) *reinterpret_cast<f32x4*>(a.out + gpos_of(zo, rt, false) * C + col) = v;
   };
 
@@ -524,17 +443,8 @@ __global__ __launch_bounds__(768, 1) void ffn_dwfc2_kernel(DwFcArgs a) {
   // wave-uniform (scalar) wave index: role branches are real branches
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int D = a.D, H = a.H, W = a.W;
-  const int ntx = (W + TX - 1) / TX, nty = (H + TY - 1) / TY, nzs = (D + a.ZS - 1) / a.ZS;
-  const int nb = gridDim.x;
-  const int xcd = blockIdx.x & 7, q8 = nb >> 3, r8 = nb & 7;
-  int t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
-  const int xt = t % ntx;
-  t /= ntx;
-  const int yt = t % nty;
-  t /= nty;
-  const int zt = t % nzs;
-  const int b = t / nzs;
-  const int x0 = xt * TX, y0 = yt * TY, z0 = zt * a.ZS, z1 = min(z0 + a.ZS, D);
+  const DwFcTile tl = dwfc_tile<TY, TX>(a);
+  const int b = tl.b, x0 = tl.x0, y0 = tl.y0, z0 = tl.z0, z1 = tl.z1;
   const int64_t plane_sz = (int64_t)H * W;
 
   for (int i = tid; i < C * (HID / 8); i += K::NTH) {
@@ -542,15 +452,8 @@ __global__ __launch_bounds__(768, 1) void ffn_dwfc2_kernel(DwFcArgs a) {
     *reinterpret_cast<bf16x8*>(wf + n * K::WKP + 8 * k8) =
         *reinterpret_cast<const bf16x8*>(a.fc + (size_t)n * HID + 8 * k8);
   }
-  for (int i = tid; i < HID; i += K::NTH) {  // halved: GELU is evaluated from x / 2
-    lnw[i] = 0.5f * a.ln2_w[i];
-    lnb[i] = 0.5f * a.ln2_b[i];
-  }
-  for (int i = tid; i < C; i += K::NTH) {
-    fcb[i] = a.fc_b ? a.fc_b[i] : 0.f;
-    n2w[i] = a.stats ? a.n2_w[i] : 1.f;
-    n2b[i] = a.stats ? a.n2_b[i] : 0.f;
-  }
+  dwfc_stage_ln2<HID>(lnw, lnb, a, K::NTH);
+  dwfc_stage_epi<C>(fcb, n2w, n2b, a, K::NTH);
   for (int i = tid; i < HID * 27; i += K::NTH) plane[i] = a.dw_w[i];
   __syncthreads();  // S0
 
@@ -719,22 +622,10 @@ __global__ __launch_bounds__(768, 1) void ffn_dwfc2_kernel(DwFcArgs a) {
           const int k = ks * 32 + 8 * g4;
           const bf16x8 bh = *reinterpret_cast<const bf16x8*>(Bh + k);
           const bf16x8 wh = *reinterpret_cast<const bf16x8*>(Wh + k);
-          if (SPLIT) {
-            const bf16x8 bl = *reinterpret_cast<const bf16x8*>(Bh + HID + k);
-            acc = mma32<P>(wh, bl, acc);
-            acc = mma32<P>(fwl[ks], bh, acc);
-          }
-          acc = mma32<P>(wh, bh, acc);
+          const bf16x8 bl = *reinterpret_cast<const bf16x8*>(Bh + HID + k);
+          acc = dwfc_mma3<P>(acc, wh, fwl[ks], bh, bl);
         }
-        f32x4 v = acc + *reinterpret_cast<const f32x4*>(fcb + col);
-        if (a.stats) {
-          const f32x4 nw = *reinterpret_cast<const f32x4*>(n2w + col);
-          const f32x4 nbv = *reinterpret_cast<const f32x4*>(n2b + col);
-          const f32x4 n2 = (xr - es.x) * es.y * nw + nbv;
-          v = xr + (n2 + v) * bs;
-        } else {
-          v = xr + v * bs;
-        }
+        const f32x4 v = dwfc_epilogue(acc, fcb, n2w, n2b, col, xr, es, bs, a.stats != nullptr);
         if (rv) *reinterpret_cast<f32x4*>(a.out + (gpos0 + (int64_t)zo * plane_sz) * C + col) = v;
       }
       if (more) rows(sF, K::PY);
@@ -862,12 +753,11 @@ static int launch_ffn_dwfc_sb(const DwFcArgs& a, int prec, hipStream_t s) {
 
 int launch_ffn_dwfc_s1(const DwFcArgs& a, int prec, hipStream_t s) {
   // ffn_dwfc_tb4 reads fp32 h1 (977-989 vs 1027-1043 us for ffn_dwfc_sb at B = 8,
-  // profiles/r4_ffn_tb/) and writes its output through buffer stores whose 32-bit byte offsets
-  // cover 2 GiB: bf16 h1 and larger outputs (stage 1 of a 128^3 input at B >= 43) take the
-  // SIMD-balanced kernel, which has no such limit
-  const bool tb4_fits = (int64_t)a.B * a.D * a.H * a.W * 48 * 4 < ((int64_t)1 << 31);
-  return prec != PREC_BF16 && tb4_fits ? launch_ffn_dwfc_tb4(a, prec, s)
-                                       : launch_ffn_dwfc_sb(a, prec, s);
+  // profiles/r4_ffn_tb/) and addresses x, out and one h1 plane through 32-bit buffer offsets
+  // (2 GiB): bf16 h1 and larger tensors (stage 1 of a 128^3 input at B >= 43, or one plane of
+  // 1673 x 1673 positions) take the SIMD-balanced kernel, which has no such limit
+  return prec != PREC_BF16 && ffn_dwfc_tb4_fits(a) ? launch_ffn_dwfc_tb4(a, prec, s)
+                                                   : launch_ffn_dwfc_sb(a, prec, s);
 }
 
 }  // namespace wf

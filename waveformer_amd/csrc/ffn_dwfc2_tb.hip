@@ -54,7 +54,7 @@
 // one wait that matters, for the landed DMA before barrier A, is then the constant vmcnt(6).
 // fp32 h1 only (bf16x3, fp16 modes) and outputs below 2 GiB (32-bit buffer offsets); the
 // launcher keeps ffn_dwfc2_kernel for the rest.
-#include "kernels.hpp"
+#include "ffn_dwfc_common.hpp"
 
 namespace wf {
 
@@ -116,17 +116,8 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc2_tb_kernel(DwFcArgs a) {
   const int tid = threadIdx.x;
   const int wid = tid >> 6, lane = tid & 63;
   const int D = a.D, H = a.H, W = a.W;
-  const int ntx = (W + TX - 1) / TX, nty = (H + TY - 1) / TY, nzs = (D + a.ZS - 1) / a.ZS;
-  const int nb = gridDim.x;
-  const int xcd = blockIdx.x & 7, q8 = nb >> 3, r8 = nb & 7;
-  int t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
-  const int xt = t % ntx;
-  t /= ntx;
-  const int yt = t % nty;
-  t /= nty;
-  const int zt = t % nzs;
-  const int b = t / nzs;
-  const int x0 = xt * TX, y0 = yt * TY, z0 = zt * a.ZS, z1 = min(z0 + a.ZS, D);
+  const DwFcTile tl = dwfc_tile<TY, TX>(a);
+  const int b = tl.b, x0 = tl.x0, y0 = tl.y0, z0 = tl.z0, z1 = tl.z1;
   const int plane_sz = H * W;
 
   if (tid < 4) simd_cnt[tid] = 0;
@@ -135,28 +126,12 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc2_tb_kernel(DwFcArgs a) {
     *reinterpret_cast<bf16x8*>(wf + n * WKP + 8 * k8) =
         *reinterpret_cast<const bf16x8*>(a.fc + (size_t)n * HID + 8 * k8);
   }
-  for (int i = tid; i < HID; i += 1024) {
-    lnw[i] = 0.5f * a.ln2_w[i];
-    lnb[i] = 0.5f * a.ln2_b[i];
-  }
-  for (int i = tid; i < C; i += 1024) {
-    fcb[i] = a.fc_b ? a.fc_b[i] : 0.f;
-    n2w[i] = a.stats ? a.n2_w[i] : 1.f;
-    n2b[i] = a.stats ? a.n2_b[i] : 0.f;
-  }
+  dwfc_stage_ln2<HID>(lnw, lnb, a, 1024);
+  dwfc_stage_epi<C>(fcb, n2w, n2b, a, 1024);
   for (int i = tid; i < HID * 27; i += 1024) plane[i] = a.dw_w[i];
   for (int i = tid; i < HID; i += 1024) plane[HID * 27 + i] = a.dw_b[i];
   __syncthreads();
-  // roles by SIMD arrival slot (tb4's rule): slots 0..2 -> D waves, slot 3 -> the E wave; if a
-  // SIMD did not get exactly four waves the roles fall back to wave-id order
-  const int simd = tb_simd_id();
-  int slot = 0;
-  if (lane == 0) slot = atomicAdd(&simd_cnt[simd], 1);
-  slot = __builtin_amdgcn_readfirstlane(__shfl(slot, 0, 64));
-  __syncthreads();
-  const bool even = simd_cnt[0] == 4 && simd_cnt[1] == 4 && simd_cnt[2] == 4 && simd_cnt[3] == 4;
-  int role = even ? (slot < 3 ? 3 * simd + slot : 12 + simd) : wid;
-  role = __builtin_amdgcn_readfirstlane(role);
+  const int role = dwfc_wave_role<4>(simd_cnt, wid, lane);  // 0..11 D, 12..15 E
   PROBE_DECL
 #ifdef WF_DWFC2_PROBE
   pr_acc[6] = role;
@@ -179,48 +154,9 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc2_tb_kernel(DwFcArgs a) {
     const float* q0 = plane + 2 * xp * HID + c;
     const int dbg = ffn_dbg(a);  // WF_FFN_DBG builds only
 
+    // the 32 lanes of a row are one half of this wave
     auto ln2_rows = [&]() {
-      constexpr int LNC = HID / 32;
-      float* row = h2t + lpos * HS;
-      float v[LNC];
-#pragma unroll
-      for (int j = 0; j < LNC / 4; ++j) {
-        const f32x4 u = *reinterpret_cast<const f32x4*>(row + 4 * lg + 128 * j);
-        v[4 * j] = u.x;
-        v[4 * j + 1] = u.y;
-        v[4 * j + 2] = u.z;
-        v[4 * j + 3] = u.w;
-      }
-      // short dependency chains, as tb4: three-way column sums, four variance partials
-      float s4[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s4[j] = (v[j] + v[j + 4]) + v[j + 8];
-      const float mean = group_sum<32>((s4[0] + s4[1]) + (s4[2] + s4[3])) * (1.f / HID);
-      float q4[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float d0 = v[j] - mean, d1 = v[j + 4] - mean, d2 = v[j + 8] - mean;
-        q4[j] = d2 * d2 + (d1 * d1 + d0 * d0);
-      }
-      const float rstd =
-          rsqrtf(group_sum<32>((q4[0] + q4[1]) + (q4[2] + q4[3])) * (1.f / HID) + a.eps2);
-      const float nmr = -mean * rstd;
-      // in place as bf16 {hi[HID], lo[HID]}: the 32 lanes of a row are one half of this wave,
-      // so all its reads precede its writes
-      uint16_t* rowh = reinterpret_cast<uint16_t*>(row);
-#pragma unroll
-      for (int j = 0; j < LNC / 4; ++j) {
-        const int cc = 4 * lg + 128 * j;
-        const f32x4 lw4 = *reinterpret_cast<const f32x4*>(lnw + cc);
-        const f32x4 lb4 = *reinterpret_cast<const f32x4*>(lnb + cc);
-        const f32x4 y = gelu_half4((f32x4{v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]} *
-                                    rstd + nmr) * lw4 + lb4);
-        uint32_t h0, h1, l0, l1;
-        split_pair<P>(y[0], y[1], h0, l0);
-        split_pair<P>(y[2], y[3], h1, l1);
-        *reinterpret_cast<u32x2*>(rowh + cc) = u32x2{h0, h1};
-        if (SPLIT) *reinterpret_cast<u32x2*>(rowh + HID + cc) = u32x2{l0, l1};
-      }
+      dwfc_ln2_row<P, HID, 32, 128, false>(h2t + lpos * HS, 4 * lg, lnw, lnb, a.eps2);
     };
     auto load_plane = [&](float (&vin)[PY][4]) {
 #pragma unroll
@@ -338,7 +274,6 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc2_tb_kernel(DwFcArgs a) {
     for (int ks = 0; ks < KH; ++ks)
       fwh[ks] = SPLIT ? *reinterpret_cast<const bf16x8*>(wh + ks * 32) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
   }
-  constexpr int OOR = (int)0x80000000;  // a buffer offset beyond every descriptor's range
   const float* src = reinterpret_cast<const float*>(a.h1) + (int64_t)b * D * plane_sz * HID;
   const int64_t plane_elems = (int64_t)plane_sz * HID;
   // plane p into the plane buffer: NPCE pieces per wave whatever e is (the padded ones repeat
@@ -355,8 +290,7 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc2_tb_kernel(DwFcArgs a) {
   auto stage = [&](int p) {
     const bool pz = p >= 0 && p < D && p <= z1 && !(dbg & 8);
     const float* base = src + (int64_t)min(max(p, 0), D - 1) * plane_elems - HID;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(base), 0, pz ? (int)((plane_elems + HID) * 4) : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = buf_rsrc(base, pz ? (int)((plane_elems + HID) * 4) : 0);
     int ln = lane, es = e;
     asm volatile("" : "+v"(ln), "+s"(es));
     const int l16 = ln * 16, hbit = ln >= 32 ? 2 : 1;
@@ -369,7 +303,7 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc2_tb_kernel(DwFcArgs a) {
       const bool rowok = yy >= 0 && yy < H;
       // bit 0 / 1: the lower / upper 32 lanes are inside the volume (a scalar)
       const int okbits = (rowok && xlo >= 0 && xlo < W ? 1 : 0) | (rowok && xhi >= 0 && xhi < W ? 2 : 0);
-      const int voff = (okbits & hbit) ? l16 : OOR;
+      const int voff = (okbits & hbit) ? l16 : BUF_OOR;
       const int soff = (max(yy, 0) * W + x0) * (HID * 4) + q * 1024;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(
           rs, (__attribute__((address_space(3))) void*)(plane + j * 256), 16, voff, soff, 0, 0);
@@ -382,12 +316,9 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc2_tb_kernel(DwFcArgs a) {
   const int gpos0 = b * D * plane_sz + min(yo, H - 1) * W + min(xo, W - 1);
   const float* sbase = a.stats ? a.stats : a.x;
   const int64_t npos = (int64_t)a.B * D * plane_sz;
-  const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.x), 0, (int)(npos * C * 4), 0x00020000);
-  const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(sbase), 0, (int)(npos * 2 * 4), 0x00020000);
-  const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(
-      a.out, 0, (int)(npos * C * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t xrsrc = buf_rsrc(a.x, (int)(npos * C * 4));
+  const __amdgpu_buffer_rsrc_t srsrc = buf_rsrc(sbase, (int)(npos * 2 * 4));
+  const __amdgpu_buffer_rsrc_t orsrc = buf_rsrc(a.out, (int)(npos * C * 4));
   f32x4 xrf = f32x4{0.f, 0.f, 0.f, 0.f}, xrh = xrf;  // residual rows: whole / straddled tile
   f32x2 esf = f32x2{0.f, 1.f}, esh = esf;
   // residual + statistics rows of output plane z (clamped: a plane outside the segment is
@@ -395,21 +326,13 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc2_tb_kernel(DwFcArgs a) {
   auto load_resid = [&](int z, int col, bool own, f32x4& xv, f32x2& ev) {
     const int g = gpos0 + min(max(z, 0), D - 1) * plane_sz;
     xv = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                       xrsrc, own ? (g * C + col) * 4 : OOR, 0, 0));
-    ev = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(srsrc, own ? g * 8 : OOR, 0, 0));
+                                       xrsrc, own ? (g * C + col) * 4 : BUF_OOR, 0, 0));
+    ev = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(srsrc, own ? g * 8 : BUF_OOR, 0, 0));
   };
-  // ffn_dwfc2_kernel's epilogue expression + a range-checked store (dropped when !ok)
+  // the epilogue + a range-checked store (dropped when !ok)
   auto epi_store = [&](f32x4 acc, int z, int col, bool ok, const f32x4& xv, const f32x2& ev) {
-    f32x4 v = acc + *reinterpret_cast<const f32x4*>(fcb + col);
-    if (a.stats) {
-      const f32x4 nw = *reinterpret_cast<const f32x4*>(n2w + col);
-      const f32x4 nbv = *reinterpret_cast<const f32x4*>(n2b + col);
-      const f32x4 n2 = (xv - ev.x) * ev.y * nw + nbv;
-      v = xv + (n2 + v) * bs;
-    } else {
-      v = xv + v * bs;
-    }
-    const int voff = ok ? ((gpos0 + z * plane_sz) * C + col) * 4 : OOR;
+    const f32x4 v = dwfc_epilogue(acc, fcb, n2w, n2b, col, xv, ev, bs, a.stats != nullptr);
+    const int voff = ok ? ((gpos0 + z * plane_sz) * C + col) * 4 : BUF_OOR;
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), orsrc, voff, 0, 0);
   };
   f32x4 acch = f32x4{0.f, 0.f, 0.f, 0.f};  // this wave's k half of the straddled tile
@@ -423,14 +346,6 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc2_tb_kernel(DwFcArgs a) {
   const uint16_t* Bh = reinterpret_cast<const uint16_t*>(h2t) + (size_t)l15 * (2 * HS) + 8 * g4;
   const uint16_t* Wf = wf + (size_t)(tf * 16 + l15) * WKP + 8 * g4;
   const uint16_t* Wh = wf + (size_t)(th * 16 + l15) * WKP + 8 * g4;
-  // one k-step: the product order of ffn_dwfc2_kernel (hi * lo, lo * hi, hi * hi)
-  auto kstep = [&](f32x4 acc, const bf16x8& bh, const bf16x8& bl, const bf16x8& wh, const bf16x8& wl) {
-    if (SPLIT) {
-      acc = mma32<P>(wh, bl, acc);
-      acc = mma32<P>(wl, bh, acc);
-    }
-    return mma32<P>(wh, bh, acc);
-  };
   auto lds8 = [](const uint16_t* q) { return *reinterpret_cast<const bf16x8*>(q); };
   // both tiles of this wave over the LN2'd h2 tile.  The straddled tile's k-steps are the whole
   // tile's steps 0..5 (even E waves) or 6..11 (odd) and use the lo fragments 0..5 either way.
@@ -439,11 +354,15 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc2_tb_kernel(DwFcArgs a) {
   auto fc = [&](f32x4& accf) {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      accf = kstep(accf, lds8(Bh + ks * 32), lds8(Bh + (SPLIT ? HID : 0) + ks * 32),
-                   lds8(Wf + ks * 32), fwf[ks]);
-      if (ks < KH)
-        acch = kstep(acch, lds8(Bh + (kh0 + ks) * 32), lds8(Bh + (SPLIT ? HID : 0) + (kh0 + ks) * 32),
-                     lds8(Wh + (kh0 + ks) * 32), fwh[ks]);
+      {
+        const bf16x8 bh = lds8(Bh + ks * 32), bl = lds8(Bh + (SPLIT ? HID : 0) + ks * 32);
+        accf = dwfc_mma3<P>(accf, lds8(Wf + ks * 32), fwf[ks], bh, bl);
+      }
+      if (ks < KH) {
+        const int k = (kh0 + ks) * 32;
+        const bf16x8 bh = lds8(Bh + k), bl = lds8(Bh + (SPLIT ? HID : 0) + k);
+        acch = dwfc_mma3<P>(acch, lds8(Wh + k), fwh[ks], bh, bl);
+      }
     }
   };
 

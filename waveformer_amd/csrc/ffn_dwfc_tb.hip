@@ -48,7 +48,7 @@
 // (The 3 x 8 one-barrier predecessor, the first E-wave memory pipeline and the round-4..8
 // schedule -- every E wave staging a quarter plane in phase 1, fc in phase 2 -- are in git
 // history.)
-#include "kernels.hpp"
+#include "ffn_dwfc_common.hpp"
 
 namespace wf {
 
@@ -119,24 +119,14 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc_tb4_kernel(DwFcArgs a) {
   const int tid = threadIdx.x;
   const int wid = tid >> 6, lane = tid & 63;
   const int D = a.D, H = a.H, W = a.W;
-  const int ntx = (W + TX - 1) / TX, nty = (H + TY - 1) / TY, nzs = (D + a.ZS - 1) / a.ZS;
-  const int nb = gridDim.x;
-  const int xcd = blockIdx.x & 7, q8 = nb >> 3, r8 = nb & 7;
-  int t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
-  const int xt = t % ntx;
-  t /= ntx;
-  const int yt = t % nty;
-  t /= nty;
-  const int zt = t % nzs;
-  const int b = t / nzs;
-  const int x0 = xt * TX, y0 = yt * TY, z0 = zt * a.ZS, z1 = min(z0 + a.ZS, D);
+  const DwFcTile tl = dwfc_tile<TY, TX>(a);
+  const int b = tl.b, x0 = tl.x0, y0 = tl.y0, z0 = tl.z0, z1 = tl.z1;
   const int64_t plane_sz = (int64_t)H * W;
 
   if (tid < 4) simd_cnt[tid] = 0;
-  for (int i = tid; i < HID; i += 1024) {
-    lnw[i] = 0.5f * a.ln2_w[i];
-    lnb[i] = 0.5f * a.ln2_b[i];
-  }
+  dwfc_stage_ln2<HID>(lnw, lnb, a, 1024);
+  // not dwfc_stage_epi: this kernel folds norm2's bias into the fc bias (one LDS read and one
+  // add less per output quad in the epilogue), a different association of the same sum
   for (int i = tid; i < C; i += 1024) {
     fcl[i] = (a.fc_b ? a.fc_b[i] : 0.f) + (a.stats ? a.n2_b[i] : 0.f);
     n2w[i] = a.stats ? a.n2_w[i] : 1.f;
@@ -151,14 +141,7 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc_tb4_kernel(DwFcArgs a) {
   for (int i = tid; i < HID * 27; i += 1024) planes[i] = a.dw_w[i];
   for (int i = tid; i < HID; i += 1024) planes[HID * 27 + i] = a.dw_b[i];
   __syncthreads();
-  const int simd = tb_simd_id();
-  int slot = 0;
-  if (lane == 0) slot = atomicAdd(&simd_cnt[simd], 1);
-  slot = __builtin_amdgcn_readfirstlane(__shfl(slot, 0, 64));
-  __syncthreads();
-  const bool even = simd_cnt[0] == 4 && simd_cnt[1] == 4 && simd_cnt[2] == 4 && simd_cnt[3] == 4;
-  int role = even ? (slot < 3 ? 3 * simd + slot : 12 + simd) : wid;
-  role = __builtin_amdgcn_readfirstlane(role);
+  const int role = dwfc_wave_role<4>(simd_cnt, wid, lane);  // 0..11 D, 12..15 E
   PROBE_DECL
 #ifdef WF_DWFC2_PROBE
   pr_acc[6] = role;
@@ -185,44 +168,7 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc_tb4_kernel(DwFcArgs a) {
     __syncthreads();  // (prologue) plane z0-1 staged
 
     auto ln2_rows = [&](float* h2t) {
-      constexpr int LNC = HID / 16;
-      float* row = h2t + lpos * HS;
-      float v[LNC];
-#pragma unroll
-      for (int j = 0; j < LNC / 4; ++j) {
-        const f32x4 u = *reinterpret_cast<const f32x4*>(row + cm + 64 * j);
-        v[4 * j] = u.x;
-        v[4 * j + 1] = u.y;
-        v[4 * j + 2] = u.z;
-        v[4 * j + 3] = u.w;
-      }
-      float s4[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s4[j] = (v[j] + v[j + 4]) + v[j + 8];
-      const float mean = group_sum<16>((s4[0] + s4[1]) + (s4[2] + s4[3])) * (1.f / HID);
-      float q4[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float d0 = v[j] - mean, d1 = v[j + 4] - mean, d2 = v[j + 8] - mean;
-        q4[j] = d2 * d2 + (d1 * d1 + d0 * d0);
-      }
-      const float rstd = __builtin_amdgcn_rsqf(
-          group_sum<16>((q4[0] + q4[1]) + (q4[2] + q4[3])) * (1.f / HID) + a.eps2);
-      const float nmr = -mean * rstd;
-      uint16_t* rowh = reinterpret_cast<uint16_t*>(row);
-#pragma unroll
-      for (int j = 0; j < LNC / 4; ++j) {
-        const int cc = cm + 64 * j;
-        const f32x4 lw4 = *reinterpret_cast<const f32x4*>(lnw + cc);
-        const f32x4 lb4 = *reinterpret_cast<const f32x4*>(lnb + cc);
-        const f32x4 y = gelu_half4((f32x4{v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]} *
-                                    rstd + nmr) * lw4 + lb4);
-        uint32_t h0, h1, l0, l1;
-        split_pair<P>(y[0], y[1], h0, l0);
-        split_pair<P>(y[2], y[3], h1, l1);
-        *reinterpret_cast<u32x2*>(rowh + cc) = u32x2{h0, h1};
-        if (SPLIT) *reinterpret_cast<u32x2*>(rowh + HID + cc) = u32x2{l0, l1};
-      }
+      dwfc_ln2_row<P, HID, 16, 64, true>(h2t + lpos * HS, cm, lnw, lnb, a.eps2);
     };
     auto rows = [&](const float (&vin)[PY][4], auto SAc, auto SBc, auto SCc, auto LOc, auto HIc) {
       constexpr int SA = decltype(SAc)::value, SB = decltype(SBc)::value,
@@ -330,7 +276,7 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc_tb4_kernel(DwFcArgs a) {
     //   p = z0 - 1 .. z1 + 1 tests p + 1 <= z1 and p + 2 <= z1 itself, so a segment of any length
     //   (the last, ragged one included) takes this one loop; no piece beyond 45 per plane, no
     //   padding.  Out-of-volume planes go through a zero-size descriptor and out-of-volume
-    //   positions through offset 0x80000000: both land as zeros.
+    //   positions through offset BUF_OOR: both land as zeros.
     // * At most 45 + FA pieces are outstanding (a whole plane and the next one's part A), within
     //   the 6-bit vmcnt.
     const float* src = reinterpret_cast<const float*>(a.h1) + (int64_t)b * D * H * W * HID;
@@ -343,15 +289,14 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc_tb4_kernel(DwFcArgs a) {
       const int pos = i / NV, v = i - pos * NV;
       const int yy = y0 - 1 + pos / PX, xx = x0 - 1 + pos % PX;
       const bool ok = yy >= 0 && yy < H && xx >= 0 && xx < W;
-      off[j] = ok ? (uint32_t)(((yy * W + xx) * HID + 4 * v) * 4) : 0x80000000u;
+      off[j] = ok ? (uint32_t)(((yy * W + xx) * HID + 4 * v) * 4) : (uint32_t)BUF_OOR;
     }
     auto fill = [&](int p, auto LOc, auto HIc) {
       constexpr int LO = decltype(LOc)::value, HI = decltype(HIc)::value;
       float* dst = planes + ((p - z0 + 1) & 1) * PLANE_F;
       const bool pz = p >= 0 && p < D;
       const float* base = src + (int64_t)min(max(p, 0), D - 1) * plane_elems;
-      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-          const_cast<float*>(base), 0, pz ? (int)(plane_elems * 4) : 0, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rs = buf_rsrc(base, pz ? (int)(plane_elems * 4) : 0);
 #pragma unroll
       for (int j = LO; j < HI; ++j)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(
@@ -429,10 +374,8 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc_tb4_kernel(DwFcArgs a) {
   f32x4 xr[2][2];
   f32x2 es[2][2];
   const int64_t npos = (int64_t)a.B * D * plane_sz;
-  const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.x), 0, (int)(npos * C * 4), 0x00020000);
-  const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(sbase), 0, (int)(npos * 2 * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t xrsrc = buf_rsrc(a.x, (int)(npos * C * 4));
+  const __amdgpu_buffer_rsrc_t srsrc = buf_rsrc(sbase, (int)(npos * 2 * 4));
   auto load_resid = [&](int zo, f32x4 (&xv)[2], f32x2 (&ev)[2]) {
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt) {
@@ -441,8 +384,7 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc_tb4_kernel(DwFcArgs a) {
       ev[rt] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(srsrc, g * 8, 0, 0));
     }
   };
-  const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(
-      a.out, 0, (int)(npos * C * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t orsrc = buf_rsrc(a.out, (int)(npos * C * 4));
   auto fc_store = [&](const float* h2t, int zo, int rt, const f32x4& xv, const f32x2& ev) {
     const int lp = rt * 16 + l15;
     f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -450,13 +392,8 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc_tb4_kernel(DwFcArgs a) {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       const int k = ks * 32 + 8 * g4;
-      const bf16x8 bh = *reinterpret_cast<const bf16x8*>(Bh + k);
-      if (SPLIT) {
-        const bf16x8 bl = *reinterpret_cast<const bf16x8*>(Bh + HID + k);
-        acc = mma32<P>(fwh[ks], bl, acc);
-        acc = mma32<P>(fwl[ks * 64], bh, acc);
-      }
-      acc = mma32<P>(fwh[ks], bh, acc);
+      acc = dwfc_mma3<P>(acc, fwh[ks], fwl[ks * 64], *reinterpret_cast<const bf16x8*>(Bh + k),
+                         *reinterpret_cast<const bf16x8*>(Bh + HID + k));
     }
     // fc + bias (+ norm2's bias, folded) and, with stats, norm2's normalised x * weight
     f32x4 v = acc + *reinterpret_cast<const f32x4*>(fcl + col);
@@ -466,7 +403,7 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc_tb4_kernel(DwFcArgs a) {
     } else {
       v = xv + v * bs;
     }
-    const int voff = row_ok(rt) ? (int)((gpos_of(zo, rt, false) * C + col) * 4) : (int)0x80000000;
+    const int voff = row_ok(rt) ? (int)((gpos_of(zo, rt, false) * C + col) * 4) : BUF_OOR;
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), orsrc, voff, 0, 0);
   };
 
@@ -540,8 +477,8 @@ int launch_ffn_dwfc_tb4(const DwFcArgs& a, int prec, hipStream_t s) {
   g.dbg = ffn_dbg_env();
   const int64_t blocks = base * cdiv(g.D, g.ZS);
   if (prec != PREC_SPLIT && prec != PREC_FP16) return fail(WF_E_SHAPE, "ffn_dwfc_tb4: fp32 h1 only");
-  if ((int64_t)g.B * g.D * g.H * g.W * C * 4 >= ((int64_t)1 << 31))
-    return fail(WF_E_SHAPE, "ffn_dwfc_tb4: output beyond the 2 GiB buffer-store range");
+  if (!ffn_dwfc_tb4_fits(g))
+    return fail(WF_E_SHAPE, "ffn_dwfc_tb4: tensor beyond the 2 GiB buffer-offset range");
   void (*kern)(DwFcArgs) = prec == PREC_SPLIT ? ffn_dwfc_tb4_kernel<PREC_SPLIT>
                                               : ffn_dwfc_tb4_kernel<PREC_FP16>;
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(1024), 0, s, g);  // static LDS

@@ -25,7 +25,7 @@
 //       h2 tile (16 lanes per position);
 //   S4  six waves run the fc GEMM (2 position tiles x 3 channel tiles, x3 for the split) and
 //       the Q4 epilogue; the other waves run ahead into the next plane's scatter.
-#include "kernels.hpp"
+#include "ffn_dwfc_common.hpp"
 
 namespace wf {
 
@@ -82,17 +82,8 @@ __global__ __launch_bounds__(ff::NTH, 1) void ffn_fused_kernel(DwFcArgs a) {
   const int D = a.D, H = a.H, W = a.W;
 
   // ---- tile of this workgroup (XCD-contiguous: neighbouring tiles share halo x rows in L2)
-  const int ntx = (W + TX - 1) / TX, nty = (H + TY - 1) / TY, nzs = (D + a.ZS - 1) / a.ZS;
-  const int nb = gridDim.x;
-  const int xcd = blockIdx.x & 7, q8 = nb >> 3, r8 = nb & 7;
-  int t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
-  const int xt = t % ntx;
-  t /= ntx;
-  const int yt = t % nty;
-  t /= nty;
-  const int zt = t % nzs;
-  const int b = t / nzs;
-  const int x0 = xt * TX, y0 = yt * TY, z0 = zt * a.ZS, z1 = min(z0 + a.ZS, D);
+  const DwFcTile tl = dwfc_tile<TY, TX>(a);
+  const int b = tl.b, x0 = tl.x0, y0 = tl.y0, z0 = tl.z0, z1 = tl.z1;
 
   // ---- per-workgroup constants into LDS
   for (int i = tid; i < 2 * HID * (C / 8); i += NTH) {
@@ -118,17 +109,12 @@ __global__ __launch_bounds__(ff::NTH, 1) void ffn_fused_kernel(DwFcArgs a) {
     pwb[i] = a.pw_b ? a.pw_b[i] : 0.f;
     l1w[i] = 0.5f * a.ln1_w[i];
     l1b[i] = 0.5f * a.ln1_b[i];
-    l2w[i] = 0.5f * a.ln2_w[i];
-    l2b[i] = 0.5f * a.ln2_b[i];
   }
+  dwfc_stage_ln2<HID>(l2w, l2b, a, NTH);
   // depthwise weights, coalesced into the (still unused) u1 plane, read back per thread below
   for (int i = tid; i < HID * 27; i += NTH) u1[i] = a.dw_w[i];
   __syncthreads();
-  for (int i = tid; i < C; i += NTH) {
-    fcb[i] = a.fc_b ? a.fc_b[i] : 0.f;
-    n2w[i] = a.stats ? a.n2_w[i] : 1.f;
-    n2b[i] = a.stats ? a.n2_b[i] : 0.f;
-  }
+  dwfc_stage_epi<C>(fcb, n2w, n2b, a, NTH);
 
   // ---- depthwise role: channel pair cp, column xi
   const int cp = tid % (HID / 2), xi = tid / (HID / 2);
@@ -415,23 +401,11 @@ __global__ __launch_bounds__(ff::NTH, 1) void ffn_fused_kernel(DwFcArgs a) {
         const int k = ks * 32 + 8 * lg4;
         const bf16x8 bh = *reinterpret_cast<const bf16x8*>(Bh + k);
         const bf16x8 wh = *reinterpret_cast<const bf16x8*>(Wh + k);
-        if (SPLIT) {
-          const bf16x8 bl = *reinterpret_cast<const bf16x8*>(Bh + HID + k);
-          const bf16x8 wl = *reinterpret_cast<const bf16x8*>(Wh + C * WKP + k);
-          acc = mma32<P>(wh, bl, acc);
-          acc = mma32<P>(wl, bh, acc);
-        }
-        acc = mma32<P>(wh, bh, acc);
+        const bf16x8 bl = *reinterpret_cast<const bf16x8*>(Bh + HID + k);
+        const bf16x8 wl = *reinterpret_cast<const bf16x8*>(Wh + C * WKP + k);
+        acc = dwfc_mma3<P>(acc, wh, wl, bh, bl);
       }
-      f32x4 v = acc + *reinterpret_cast<const f32x4*>(fcb + col);
-      if (a.stats) {
-        const f32x4 lw = *reinterpret_cast<const f32x4*>(n2w + col);
-        const f32x4 lb = *reinterpret_cast<const f32x4*>(n2b + col);
-        const f32x4 n2 = (xr_c - es_c.x) * es_c.y * lw + lb;
-        v = xr_c + (n2 + v) * bs;
-      } else {
-        v = xr_c + v * bs;
-      }
+      const f32x4 v = dwfc_epilogue(acc, fcb, n2w, n2b, col, xr_c, es_c, bs, a.stats != nullptr);
       if (rv) *reinterpret_cast<f32x4*>(a.out + gpos * C + col) = v;
     }
 #pragma unroll

@@ -182,104 +182,7 @@ int launch_dwconv3d(const void* in, const float* w, const float* b, void* out, f
 int launch_ln_stats_finalize(const float* pstats, int np, int group, float eps, float* out,
                              int64_t M, hipStream_t s);
 constexpr int DW_STAT_GROUP = 32;
-// ---- CCF_FFN back half fused (ffn_dwfc.hip): dwconv + bias + LN2 + GELU + fc + bias + the
-// Block's Q4 residual, for C = 48, hidden = 192 (h1 fp32 for PREC_SPLIT, bf16 for PREC_BF16)
-struct DwFcArgs {
-  const void* h1;        // (B, D, H, W, HID) fp32 (SPLIT) or bf16
-  const float* dw_w;     // (HID, 27)
-  const float* dw_b;     // (HID)
-  const float* ln2_w;    // (HID)
-  const float* ln2_b;
-  float eps2;
-  const uint16_t* fc;    // [2][C][HID] bf16 {hi, lo}
-  const float* fc_b;     // (C) or NULL
-  const float* x;        // (B, D, H, W, C) residual rows
-  const float* stats;    // (M, 2) {mean, rstd} of x for norm2, or NULL
-  const float* n2_w;
-  const float* n2_b;
-  const float* bscale;   // (B) or NULL
-  float* out;            // (B, D, H, W, C)
-  int B, D, H, W, ZS;
-  // whole-FFN kernel (ffn_fused.hip) only: the front half, recomputed on chip from x
-  const uint16_t* pw;    // [2][HID][C] bf16 {hi, lo}
-  const float* pw_b;     // (HID) or NULL
-  const float* ln1_w;    // (HID)
-  const float* ln1_b;
-  float eps1;
-  int dbg;               // timing experiments only (builds with WF_FFN_DBG=1): phases skipped
-};
-#ifndef WF_FFN_DBG  // 1: timing-experiment build (DwFcArgs::dbg phase skips; never the shipped library)
-#define WF_FFN_DBG 0
-#endif
-// the phases a kernel skips: none unless the build has WF_FFN_DBG=1 (results are then invalid)
-__device__ __forceinline__ int ffn_dbg(const DwFcArgs& a) { return WF_FFN_DBG ? a.dbg : 0; }
-inline int ffn_dbg_env() {
-  return WF_FFN_DBG && getenv("WF_FFN_DBG") ? atoi(getenv("WF_FFN_DBG")) : 0;
-}
-// stage-1 shape: ffn_dwfc_tb4 for fp32 h1 and outputs below 2 GiB, else ffn_dwfc_sb
-int launch_ffn_dwfc_s1(const DwFcArgs& a, int prec, hipStream_t s);
-// three VALU waves per SIMD on 4 x 8 tiles, two barriers per plane (ffn_dwfc_tb.hip)
-int launch_ffn_dwfc_tb4(const DwFcArgs& a, int prec, hipStream_t s);
-// h1 plane staging: fp32 (SPLIT / FP16 workspaces) or bf16 (BF16) rows widened to fp32
-template <typename T>
-struct H1Load;
-template <>
-struct H1Load<float> {
-  typedef f32x4 raw;
-  static __device__ __forceinline__ raw load(const float* p, int64_t i) {
-    return *reinterpret_cast<const f32x4*>(p + i);
-  }
-  static __device__ __forceinline__ f32x4 up(raw u) { return u; }
-};
-template <>
-struct H1Load<uint16_t> {
-  typedef bf16x4 raw;
-  static __device__ __forceinline__ raw load(const uint16_t* p, int64_t i) {
-    return *reinterpret_cast<const bf16x4*>(p + i);
-  }
-  static __device__ __forceinline__ f32x4 up(raw u) {
-    return f32x4{bf2f((uint16_t)u[0]), bf2f((uint16_t)u[1]), bf2f((uint16_t)u[2]),
-                 bf2f((uint16_t)u[3])};
-  }
-};
-
-// the same for C = 96, hidden = 384 (4 x 4 tiles, one plane buffer, fc weight hi in LDS):
-// ffn_dwfc2_tb for fp32 h1 and tensors below 2 GiB, else ffn_dwfc2_kernel; sets ZS
-int launch_ffn_dwfc2(const DwFcArgs& a, int prec, hipStream_t s);
-// three depthwise waves + one staging / fc wave per SIMD (ffn_dwfc2_tb.hip); ZS set by the caller
-int launch_ffn_dwfc2_tb(const DwFcArgs& a, int prec, hipStream_t s);
-// ffn_dwfc2_tb addresses x, out and one h1 plane through 32-bit buffer byte offsets
-inline bool ffn_dwfc2_tb_fits(const DwFcArgs& a) {
-  return (int64_t)a.B * a.D * a.H * a.W * 96 * 4 < ((int64_t)1 << 31) &&
-         ((int64_t)a.H * a.W + 8) * 384 * 4 < ((int64_t)1 << 31);
-}
-// HW_ID (hwreg 4) bits [5:4]: the SIMD the wave runs on
-__device__ __forceinline__ int tb_simd_id() {
-  return (int)((__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4)) & 3);
-}
-// ---- diagnostic builds only (-DWF_DWFC2_PROBE; ffn_dwfc_sb, ffn_dwfc2 and ffn_dwfc2_tb):
-// per-wave cycles of workgroup 0 by phase between the kernel's barriers, 8 slots per wave
-#ifdef WF_DWFC2_PROBE
-#define PROBE_DECL                                                              \
-  const bool probe_on = blockIdx.x == 0;                                         \
-  long long pr_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pr_last = __builtin_amdgcn_s_memtime();
-#define PROBE(i)                                                                \
-  if (probe_on) {                                                               \
-    const long long t_ = __builtin_amdgcn_s_memtime();                          \
-    pr_acc[i] += t_ - pr_last;                                                  \
-    pr_last = t_;                                                               \
-  }
-#define PROBE_DUMP_TO(arr)                                                      \
-  if (probe_on && (tid & 63) == 0)                                              \
-    for (int i_ = 0; i_ < 8; ++i_) arr[wid * 8 + i_] = pr_acc[i_];
-#else
-#define PROBE_DECL
-#define PROBE(i)
-#define PROBE_DUMP_TO(arr)
-#endif
-// ---- the whole CCF_FFN + norm2 + Q4 residual in one kernel for C = 48, hidden = 192: the
-// haloed h1 plane is computed in LDS from the x rows (pw MFMA + LN1 + GELU), never stored
-int launch_ffn_fused(const DwFcArgs& a, int prec, hipStream_t s);
+// ---- the CCF_FFN back-half kernels (DwFcArgs, launch_ffn_*): ffn_dwfc_common.hpp, below
 // K-chunked MFMA GEMM (gemm_kc.hip) for the shapes whose weight does not fit gemm_rows' LDS
 // in one column chunk; returns 1 if it took the shape
 int try_launch_gemm_kc(const GemmArgs& g, hipStream_t s);
@@ -296,3 +199,5 @@ int try_launch_gemm_lnw(const GemmArgs& g, hipStream_t s);
 bool gemm_lnw_wide_shape(const GemmArgs& g);
 
 }  // namespace wf
+
+#include "ffn_dwfc_common.hpp"
