@@ -7,6 +7,9 @@ Makefile's CXXFLAGS plus `--cuda-device-only -S`.  Directive and comment lines a
 every kernel (amdhsa kernel symbol) is then put into one class:
 
   identical      the instruction text is the same, line for line;
+  labels only    the same once the numbers of local labels are masked (.LBB<f>_<n> carries the
+                 function's index in the file, which moves when a function before it comes or
+                 goes);
   prologue only  the texts differ only before the kernel's first s_barrier and are equal after
                  it once register numbers and local labels are masked;
   body changed   anything else (a kernel without an s_barrier that differs lands here);
@@ -95,6 +98,8 @@ def first_barrier(lines):
 def classify(a, b):
     if a == b:
         return "identical"
+    if [LABEL.sub(".L", l) for l in a] == [LABEL.sub(".L", l) for l in b]:
+        return "labels only"
     ia, ib = first_barrier(a), first_barrier(b)
     if ia >= 0 and ib >= 0 and [mask(l) for l in a[ia:]] == [mask(l) for l in b[ib:]]:
         return "prologue only"

@@ -342,7 +342,7 @@ __global__ __launch_bounds__(768, 1) void ffn_dwfc_sb_kernel(DwFcArgs a) {
       const int k = ks * 32 + 8 * g4;
       const bf16x8 bh = *reinterpret_cast<const bf16x8*>(Bh + k);
       const bf16x8 bl = *reinterpret_cast<const bf16x8*>(Bh + HID + k);
-      acc = dwfc_mma3<P>(acc, fwh[ks], *reinterpret_cast<const bf16x8*>(fwl + ks * 32), bh, bl);
+      acc = mma3<P>(acc, fwh[ks], *reinterpret_cast<const bf16x8*>(fwl + ks * 32), bh, bl);
     }
     const f32x4 v = dwfc_epilogue(acc, fcb, n2w, n2b, col, xr[rt], es[rt], bs, a.stats != nullptr);
     if (row_ok(rt)) *reinterpret_cast<f32x4*>(a.out + gpos_of(zo, rt, false) * C + col) = v;
@@ -623,7 +623,7 @@ __global__ __launch_bounds__(768, 1) void ffn_dwfc2_kernel(DwFcArgs a) {
           const bf16x8 bh = *reinterpret_cast<const bf16x8*>(Bh + k);
           const bf16x8 wh = *reinterpret_cast<const bf16x8*>(Wh + k);
           const bf16x8 bl = *reinterpret_cast<const bf16x8*>(Bh + HID + k);
-          acc = dwfc_mma3<P>(acc, wh, fwl[ks], bh, bl);
+          acc = mma3<P>(acc, wh, fwl[ks], bh, bl);
         }
         const f32x4 v = dwfc_epilogue(acc, fcb, n2w, n2b, col, xr, es, bs, a.stats != nullptr);
         if (rv) *reinterpret_cast<f32x4*>(a.out + (gpos0 + (int64_t)zo * plane_sz) * C + col) = v;

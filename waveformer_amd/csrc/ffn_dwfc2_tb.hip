@@ -356,12 +356,12 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc2_tb_kernel(DwFcArgs a) {
     for (int ks = 0; ks < KS; ++ks) {
       {
         const bf16x8 bh = lds8(Bh + ks * 32), bl = lds8(Bh + (SPLIT ? HID : 0) + ks * 32);
-        accf = dwfc_mma3<P>(accf, lds8(Wf + ks * 32), fwf[ks], bh, bl);
+        accf = mma3<P>(accf, lds8(Wf + ks * 32), fwf[ks], bh, bl);
       }
       if (ks < KH) {
         const int k = (kh0 + ks) * 32;
         const bf16x8 bh = lds8(Bh + k), bl = lds8(Bh + (SPLIT ? HID : 0) + k);
-        acch = dwfc_mma3<P>(acch, lds8(Wh + k), fwh[ks], bh, bl);
+        acch = mma3<P>(acch, lds8(Wh + k), fwh[ks], bh, bl);
       }
     }
   };

@@ -245,20 +245,6 @@ __device__ __forceinline__ void dwfc_ln2_row(float* row, int q0, const float* ln
   }
 }
 
-// ---- one k-step of the fc on v_mfma_f32_16x16x32: weight fragment w (A), LN2'd h2 fragment b
-// (B).  For PREC_SPLIT the three products go hi * lo, lo * hi, hi * hi IN THIS ORDER -- the
-// order is what makes the outputs bit-stable across the kernels; the other modes have the one
-// product (the lo fragments are then unused and their loads dead).
-template <int P>
-__device__ __forceinline__ f32x4 dwfc_mma3(f32x4 acc, const bf16x8& w_hi, const bf16x8& w_lo,
-                                           const bf16x8& b_hi, const bf16x8& b_lo) {
-  if constexpr (P == PREC_SPLIT) {
-    acc = mma32<P>(w_hi, b_lo, acc);
-    acc = mma32<P>(w_lo, b_hi, acc);
-  }
-  return mma32<P>(w_hi, b_hi, acc);
-}
-
 // ---- the epilogue of four output channels col .. col + 3 of one position:
 //   out = x + (n2 + fc + fc_b) * bs,  n2 = (x - mean) * rstd * n2_w + n2_b  (the Block form:
 // norm2 + quirk Q4's double residual), or out = x + (fc + fc_b) * bs for a bare CCF_FFN.

@@ -392,7 +392,7 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc_tb4_kernel(DwFcArgs a) {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       const int k = ks * 32 + 8 * g4;
-      acc = dwfc_mma3<P>(acc, fwh[ks], fwl[ks * 64], *reinterpret_cast<const bf16x8*>(Bh + k),
+      acc = mma3<P>(acc, fwh[ks], fwl[ks * 64], *reinterpret_cast<const bf16x8*>(Bh + k),
                          *reinterpret_cast<const bf16x8*>(Bh + HID + k));
     }
     // fc + bias (+ norm2's bias, folded) and, with stats, norm2's normalised x * weight

@@ -403,7 +403,7 @@ __global__ __launch_bounds__(ff::NTH, 1) void ffn_fused_kernel(DwFcArgs a) {
         const bf16x8 wh = *reinterpret_cast<const bf16x8*>(Wh + k);
         const bf16x8 bl = *reinterpret_cast<const bf16x8*>(Bh + HID + k);
         const bf16x8 wl = *reinterpret_cast<const bf16x8*>(Wh + C * WKP + k);
-        acc = dwfc_mma3<P>(acc, wh, wl, bh, bl);
+        acc = mma3<P>(acc, wh, wl, bh, bl);
       }
       const f32x4 v = dwfc_epilogue(acc, fcb, n2w, n2b, col, xr_c, es_c, bs, a.stats != nullptr);
       if (rv) *reinterpret_cast<f32x4*>(a.out + gpos * C + col) = v;

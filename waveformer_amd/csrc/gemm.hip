@@ -1,38 +1,33 @@
-// gemm.hip -- the A-resident bf16 MFMA GEMM behind every Linear / 1x1x1 Conv3d of the path.
+// gemm.hip -- launch_gemm, the entry of every Linear / 1x1x1 Conv3d of the path, and
+// gemm_ares, the A-resident fallback GEMM.
 //
-//   qkv   (attention.py:87, with window_partition wave_helper.py:450-461 and norm1 folded in)
-//   proj  (attention.py:102)
-//   pwconv (wave_helper.py:278) + LN(4C) + GELU (:279) folded into the epilogue
-//   fc    (wave_helper.py:289) + the Block's double residual (:293 and :509, quirk Q4)
-//   PatchMerging gather + LN(8C) + reduction (wave_helper.py:183-193, quirk Q3)
+// launch_gemm hands a shape to the first kernel that takes it: gemm_lnw / pw2_res (the CCF_FFN
+// pwconv with its LayerNorm + GELU epilogue), gemm_rows (one LDS-resident weight chunk covers
+// all N), gemm_kc (the weight K-chunked through LDS).  gemm_ares takes what is left: N not a
+// multiple of 16, and the shapes neither streaming kernel takes -- a window or PatchMerging
+// gather with an epilogue other than the plain store (gemm_known_callsite), or N a multiple
+// of 16 but not of 32 whose weight does not fit gemm_rows' LDS in one column chunk.  The
+// generic wf_linear_fwd entry reaches it with such N (tests/test_gpu_gemm_family.py).
 //
 // Structure (one 256-thread workgroup = BM rows x all N columns):
 //   1. loader: the BM source rows (gathered, optionally LayerNorm'ed in fp32) are rounded to
 //      bf16 into an LDS tile A[BM][KP] (plus the residual tile A_lo for PREC_SPLIT) -- A is
 //      read from HBM exactly once.
 //   2. MFMA: each wave owns 16 columns of a 64-column chunk; per 32-deep k step it loads its
-//      Wt[n][k..k+8] fragment(s) straight from L2 (the weights are at most 1.2 MB) and issues
-//      BM/16 v_mfma_f32_16x16x32_bf16 (x3 for PREC_SPLIT: hi*hi + lo*hi + hi*lo) against A
-//      fragments read by ds_read_b128.
+//      Wt[n][k..k+8] fragment(s) straight from L2 and issues BM/16 v_mfma_f32_16x16x32_bf16
+//      (x3 for PREC_SPLIT, here in the order lo*hi + hi*lo + hi*hi with the activation as the
+//      MFMA's A operand -- not mma3's order, so the step stays inline) against A fragments read
+//      by ds_read_b128.
 //   3. the fp32 accumulators land in an LDS row buffer R[BM][N]; the epilogue then walks rows
 //      (bias, LayerNorm+GELU or residual) and writes whole rows with 16-B stores.
-// Roofline: for every call site K, N <= 1536 and the arithmetic intensity is far below the
-// bf16 ridge point, so the kernel is HBM-bound on reading A and writing the output.
-#include "kernels.hpp"
+#include "gemm_common.hpp"
 
 namespace wf {
 
+// load8f with the runtime storage flag (this kernel is not instantiated per storage type)
 __device__ __forceinline__ void load8(const void* src, int is_bf16, int64_t off, float (&v)[8]) {
-  if (is_bf16) {
-    bf16x8 u = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const uint16_t*>(src) + off);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = bf2f((uint16_t)u[j]);
-  } else {
-    const f32x4* p = reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(src) + off);
-    f32x4 a = p[0], b = p[1];
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-    v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  }
+  if (is_bf16) load8f<true>(src, off, v);
+  else load8f<false>(src, off, v);
 }
 
 // Element offset of element k of logical row m in the source.
@@ -282,26 +277,15 @@ __global__ __launch_bounds__(256) void gemm_ares_kernel(GemmArgs g) {
     } else if (g.epi == EPI_RESID) {
       const f32x4 xr = reinterpret_cast<const f32x4*>(g.r_x + m * (int64_t)N)[c4];
       const float bs = g.r_scale ? g.r_scale[m / g.rows_per_sample] : 1.f;
+      float mean = 0.f, rstd = 1.f;
       if (g.r_stats) {
-        const float mean = g.r_stats[2 * m], rstd = g.r_stats[2 * m + 1];
-        const f32x4 lw = reinterpret_cast<const f32x4*>(g.r_ln_w)[c4];
-        const f32x4 lb = reinterpret_cast<const f32x4*>(g.r_ln_b)[c4];
-        const f32x4 n2 = (xr - mean) * rstd * lw + lb;
-        v = xr + (n2 + v) * bs;  // attn_fused + drop_path(n2 + ffn(n2)), quirk Q4
-      } else {
-        v = xr + v * bs;         // bare CCF_FFN.forward: x + x_out (wave_helper.py:293)
+        mean = g.r_stats[2 * m];
+        rstd = g.r_stats[2 * m + 1];
       }
+      v = resid_epilogue(v, xr, mean, rstd, g.r_ln_w + 4 * c4, g.r_ln_b + 4 * c4, bs,
+                         g.r_stats != nullptr);
     }
-    if (g.out_bf16) {
-      bf16x4 o;
-      o[0] = (short)f2bf(v.x);
-      o[1] = (short)f2bf(v.y);
-      o[2] = (short)f2bf(v.z);
-      o[3] = (short)f2bf(v.w);
-      *reinterpret_cast<bf16x4*>(reinterpret_cast<uint16_t*>(g.out) + m * g.ldo + 4 * c4) = o;
-    } else {
-      *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(g.out) + m * g.ldo + 4 * c4) = v;
-    }
+    store4(g.out, g.out_bf16 != 0, m * g.ldo, 4 * c4, v);
   }
 }
 
@@ -337,25 +321,13 @@ int launch_gemm(const GemmArgs& g, hipStream_t s, const char* who) {
       set_max_lds(reinterpret_cast<const void*>(kern), (int)lds);
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, s, g);
   };
-  if (split) {
+  gemm_with_prec(g.prec, false, [&](auto P, auto) {  // the storage type is a runtime flag here
     switch (BM) {
-      case 64: go(gemm_ares_kernel<64, PREC_SPLIT>); break;
-      case 32: go(gemm_ares_kernel<32, PREC_SPLIT>); break;
-      default: go(gemm_ares_kernel<16, PREC_SPLIT>); break;
+      case 64: go(gemm_ares_kernel<64, P()>); break;
+      case 32: go(gemm_ares_kernel<32, P()>); break;
+      default: go(gemm_ares_kernel<16, P()>); break;
     }
-  } else if (g.prec == PREC_FP16) {
-    switch (BM) {
-      case 64: go(gemm_ares_kernel<64, PREC_FP16>); break;
-      case 32: go(gemm_ares_kernel<32, PREC_FP16>); break;
-      default: go(gemm_ares_kernel<16, PREC_FP16>); break;
-    }
-  } else {
-    switch (BM) {
-      case 64: go(gemm_ares_kernel<64, PREC_BF16>); break;
-      case 32: go(gemm_ares_kernel<32, PREC_BF16>); break;
-      default: go(gemm_ares_kernel<16, PREC_BF16>); break;
-    }
-  }
+  });
   return check_launch(who);
 }
 

@@ -1,6 +1,18 @@
-// gemm_common.hpp -- A-operand helpers shared by the streaming GEMMs (gemm_rows, gemm_kc).
+// gemm_common.hpp -- what the MFMA GEMM family (gemm.hip, gemm_rows.hip, gemm_kc.hip,
+// gemm_lnw.hip, merge.hip, pw2.hip) shares: the row loaders, the A-fragment transform, the
+// LayerNorm statistics of loader and epilogue, the residual epilogue, the four-value store and
+// the host-side kernel selection (mma3, which the CCF_FFN kernels use too, is in kernels.hpp).  The k loops, prefetch schedules and LDS layouts are the
+// kernels and stay in their files.
+//
+// Every helper presents the compiler with the expression tree of the text it replaced: FMA
+// contraction follows the shape of the expression, and two pairs of these kernels are
+// bit-identical by contract (merge_res = gemm_kc, pw2_res = gemm_lnw<3, 3, 8, 8>).
 #pragma once
+#include <type_traits>
+
 #include "kernels.hpp"
+
+namespace wf {
 
 // Row padding (bf16 elements) of the LDS operand images the MFMA fragments are read from with
 // ds_read_b128 (lane l: row l & 15, 16-B chunk l >> 4).  gfx950 serves a b128 read in four
@@ -8,12 +20,8 @@
 // a group is conflict-free iff the row stride is 8 (mod 16) dwords: 16 bf16 of padding on a
 // 32-multiple row.  The round-1..4 pad of 8 (4 dwords) left 2-way conflicts in every group
 // (SQ_LDS_BANK_CONFLICT 1.6-3.4 per LDS instruction in gemm_rows / gemm_kc / gemm_lnw,
-// profiles/r4s_encoder_sq_per_kernel.txt).  WF_LDS_KPAD=8 restores the old images for A/B.
-#ifndef WF_LDS_KPAD
-#define WF_LDS_KPAD 16
-#endif
-
-namespace wf {
+// profiles/r4s_encoder_sq_per_kernel.txt).
+constexpr int WF_LDS_KPAD = 16;
 
 template <bool BF16>
 __device__ __forceinline__ void load8f(const void* src, int64_t off, float (&v)[8]) {
@@ -72,5 +80,150 @@ struct RowMapper {
     return (int64_t)pos * g.K + k;
   }
 };
+
+// ---- LN_COMPUTE: the octets g4, g4 + 4, g4 + 8, ... of one row (the 4 lanes l15 + 16 g4 of a
+// row split its k range), four octets per batch with the loads first (a load per iteration
+// waits out one latency per octet).  The clamped tail octets are loaded again and arrive with
+// mask mk = 0: acc(x, mk) is called for every value in octet order.
+template <bool ABF16, class Off, class Acc>
+__device__ __forceinline__ void ln_row_batches(const void* src, int noct, int g4, Off off, Acc acc) {
+  for (int cb = g4; cb < noct; cb += 16) {
+    float v[4][8];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) load8f<ABF16>(src, off(min(cb + 4 * u, noct - 1) * 8), v[u]);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const float mk = cb + 4 * u < noct ? 1.f : 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc(v[u][j], mk);
+    }
+  }
+}
+
+// ---- LN_PARTIAL: the producer's np {mean, M2} partials of a row, each over K / np columns,
+// combined over the row's 4 lanes (Chan et al.)
+__device__ __forceinline__ void ln_partial_combine(const float* ps, int np, int K, float eps,
+                                                   int g4, float& mean, float& rstd) {
+  float s = 0.f;
+  for (int c = g4; c < np; c += 4) s += ps[2 * c];
+  s = xsum16(s);
+  s = xsum32(s);
+  mean = s / (float)np;
+  const float ng = (float)(K / np);
+  float q = 0.f;
+  for (int c = g4; c < np; c += 4) {
+    const float d = ps[2 * c] - mean;
+    q += ps[2 * c + 1] + ng * d * d;
+  }
+  q = xsum16(q);
+  q = xsum32(q);
+  rstd = rsqrtf(q / (float)K + eps);
+}
+
+// ---- the A fragment of one k step: the lane's octet v (columns k .. k + 7 of its row) through
+// the loader's LayerNorm (gamma / beta lnw, lnb in LDS, indexed by k), GELU, the zero-select of
+// the columns past K (kv) and the operand split.  v is left transformed.  gemm_kc and merge_res
+// both come here, so merge_res = gemm_kc holds for the transform by construction (gemm_rows'
+// kstep states the same text inline: DESIGN.md 6.17).
+template <int P>
+__device__ __forceinline__ void a_fragment(float (&v)[8], float mean, float rstd,
+                                           const float* lnw, const float* lnb, int k, bool kv,
+                                           bool has_ln, bool gelu, bf16x8& ah, bf16x8& al) {
+  if (has_ln) {
+    const f32x4 w0 = *reinterpret_cast<const f32x4*>(lnw + k);
+    const f32x4 w1 = *reinterpret_cast<const f32x4*>(lnw + k + 4);
+    const f32x4 b0 = *reinterpret_cast<const f32x4*>(lnb + k);
+    const f32x4 b1 = *reinterpret_cast<const f32x4*>(lnb + k + 4);
+    const float wv[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+    const float bv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float x = (v[j] - mean) * rstd * wv[j] + bv[j];
+      // fp16: the fp32 value first, then the operand rounding -- not a v_fma_mix straight to
+      // fp16, which a caller without the kv select (merge_res) would otherwise get
+      if (P == PREC_FP16) asm volatile("" : "+v"(x));
+      v[j] = x;
+    }
+  }
+  if (gelu) {
+    gelu_erf8(v);
+  }
+  float xs[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) xs[j] = kv ? v[j] : 0.f;
+  split8<P>(xs, ah, al);
+}
+
+// ---- row moments over a lane's NT accumulator tiles (4 values each), reduced over the 4
+// lanes of the row: the sum, and the sum of squares about `mean`
+template <int NT>
+__device__ __forceinline__ float tile_sum(const f32x4* acc) {
+  float s = 0.f;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) s += (acc[t].x + acc[t].y) + (acc[t].z + acc[t].w);
+  s = xsum16(s);
+  return xsum32(s);
+}
+template <int NT>
+__device__ __forceinline__ float tile_sqdev(const f32x4* acc, float mean) {
+  float q = 0.f;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const f32x4 d = acc[t] - mean;
+    q += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
+  }
+  q = xsum16(q);
+  return xsum32(q);
+}
+
+// ---- EPI_RESID on four channels: x + (n2 + v) * bs with n2 = (x - mean) * rstd * lw + lb
+// (attn_fused + drop_path(n2 + ffn(n2)), quirk Q4), or x + v * bs without norm2 statistics
+// (bare CCF_FFN.forward: x + x_out, wave_helper.py:293).  lw, lb: the four channels' norm2
+// affine, read only with has_stats.  The CCF_FFN back half states the same expression on its
+// staged vectors (dwfc_epilogue): written through this function, ffn_dwfc_sb / ffn_dwfc2 /
+// ffn_fused compile to other text, so it keeps its own.
+__device__ __forceinline__ f32x4 resid_epilogue(f32x4 v, f32x4 xr, float mean, float rstd,
+                                                const float* lw, const float* lb, float bs,
+                                                bool has_stats) {
+  if (!has_stats) return xr + v * bs;
+  const f32x4 w4 = *reinterpret_cast<const f32x4*>(lw);
+  const f32x4 b4 = *reinterpret_cast<const f32x4*>(lb);
+  const f32x4 n2 = (xr - mean) * rstd * w4 + b4;
+  return xr + (n2 + v) * bs;
+}
+
+// ---- four consecutive output values, bf16 (RNE) or fp32, at element offset roff + col (a row's
+// offset and a column, added to the pointer one after the other as the kernels' own text did:
+// the address arithmetic the compiler derives follows that association)
+__device__ __forceinline__ bf16x4 pack_bf16x4(f32x4 v) {
+  bf16x4 o;
+  o[0] = (short)f2bf(v.x);
+  o[1] = (short)f2bf(v.y);
+  o[2] = (short)f2bf(v.z);
+  o[3] = (short)f2bf(v.w);
+  return o;
+}
+__device__ __forceinline__ void store4(void* out, bool out_bf16, int64_t roff, int col, f32x4 v) {
+  if (out_bf16) *reinterpret_cast<bf16x4*>(reinterpret_cast<uint16_t*>(out) + roff + col) = pack_bf16x4(v);
+  else *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(out) + roff + col) = v;
+}
+
+// ---- host side
+// the call sites the streaming kernels (gemm_rows, gemm_kc) are instantiated for; the others
+// fall back to gemm_ares: window qkv, identity store / LN / resid, PatchMerging gather
+inline bool gemm_known_callsite(const GemmArgs& g) {
+  return (g.a_map == MAP_WINDOW && g.epi == EPI_STORE) || (g.a_map == MAP_IDENTITY) ||
+         (g.a_map == MAP_MERGE && g.epi == EPI_STORE);
+}
+// (prec, a_bf16) as compile-time tags: f(P, ABF16) is called with an
+// std::integral_constant<int, Prec> and an std::bool_constant.  bf16 activations only exist in
+// PREC_BF16.
+template <class F>
+inline void gemm_with_prec(int prec, bool a_bf16, F&& f) {
+  if (a_bf16) f(std::integral_constant<int, PREC_BF16>{}, std::true_type{});
+  else if (prec == PREC_SPLIT) f(std::integral_constant<int, PREC_SPLIT>{}, std::false_type{});
+  else if (prec == PREC_FP16) f(std::integral_constant<int, PREC_FP16>{}, std::false_type{});
+  else f(std::integral_constant<int, PREC_BF16>{}, std::false_type{});
+}
 
 }  // namespace wf

@@ -9,7 +9,7 @@
 //     one run, and written to the other buffer behind them (one barrier per k step);
 //   * A fragments come straight from global memory into registers (lane l: row l&15,
 //     k = 8*(l>>4) .. +7 of the step), one step ahead, through the row gather / LayerNorm /
-//     GELU / bf16 hi-lo split of gemm_common.hpp's RowMapper;
+//     GELU / bf16 hi-lo split (gemm_common.hpp: RowMapper, a_fragment);
 //   * transposed MFMA (weight fragment = A operand), so each lane ends with 4 consecutive
 //     output channels of one row: 16-byte epilogue loads and stores.
 // LayerNorm of A: LN_GIVEN (stats passed in), LN_COMPUTE (one shifted sum / sum-of-squares
@@ -121,24 +121,13 @@ __global__ __launch_bounds__(64 * WV) void gemm_kc_kernel(GemmArgs g) {
       load8f<ABF16>(g.a_src, rm.offset(g, 0), v0);
       const float sh = v0[0];
       float s = 0.f, q = 0.f;
-      // four octets per batch, loads first: the round-3 loop waited out one load latency per
-      // octet (12 in a row at K = 384); same summation order, the clamped tail octets add 0
-      const int noct = K / 8;
-      for (int cb = g4; cb < noct; cb += 16) {
-        float v[4][8];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) load8f<ABF16>(g.a_src, rm.offset(g, min(cb + 4 * u, noct - 1) * 8), v[u]);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const float mk = cb + 4 * u < noct ? 1.f : 0.f;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const float d = (v[u][j] - sh) * mk;
-            s += d;
-            q += d * d;
-          }
-        }
-      }
+      // (ln_row_batches: four octets per batch, 12 loads in a row at K = 384 otherwise)
+      ln_row_batches<ABF16>(g.a_src, K / 8, g4, [&](int k) { return rm.offset(g, k); },
+                            [&](float x, float mk) {
+                              const float d = (x - sh) * mk;
+                              s += d;
+                              q += d * d;
+                            });
       s = xsum16(s);
       s = xsum32(s);
       q = xsum16(q);
@@ -148,26 +137,10 @@ __global__ __launch_bounds__(64 * WV) void gemm_kc_kernel(GemmArgs g) {
       rstd[rt] = rsqrtf(fmaxf(q / (float)K - ms * ms, 0.f) + g.a_eps);
     }
   } else if (g.a_ln == LN_PARTIAL) {
-    const int np = g.a_np;
-    const float ng = (float)(K / np);
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-      const float* ps = g.a_stats + (int64_t)arow[rt] * np * 2;
-      float s = 0.f;
-      for (int c = g4; c < np; c += 4) s += ps[2 * c];
-      s = xsum16(s);
-      s = xsum32(s);
-      const float mu = s / (float)np;
-      float q = 0.f;
-      for (int c = g4; c < np; c += 4) {
-        const float d = ps[2 * c] - mu;
-        q += ps[2 * c + 1] + ng * d * d;
-      }
-      q = xsum16(q);
-      q = xsum32(q);
-      mean[rt] = mu;
-      rstd[rt] = rsqrtf(q / (float)K + g.a_eps);
-    }
+    for (int rt = 0; rt < RT; ++rt)
+      ln_partial_combine(g.a_stats + (int64_t)arow[rt] * g.a_np * 2, g.a_np, K, g.a_eps, g4, mean[rt],
+                         rstd[rt]);
   }
 
   f32x4 acc[RT][NT];
@@ -220,35 +193,10 @@ __global__ __launch_bounds__(64 * WV) void gemm_kc_kernel(GemmArgs g) {
       for (int j = 0; j < 8; ++j) v[rt][j] = vin[rt][j];
     wfetch(min(ks + 2, ks1 - 1), wst[S]);  // two steps ahead (tail steps: unused re-reads)
     bf16x8 ah[RT], al[RT];
-    {
-      float wv[8], bv[8];
-      if (g.a_ln != LN_NONE) {
-        const f32x4 w0 = *reinterpret_cast<const f32x4*>(lnw + k);
-        const f32x4 w1 = *reinterpret_cast<const f32x4*>(lnw + k + 4);
-        const f32x4 b0 = *reinterpret_cast<const f32x4*>(lnb + k);
-        const f32x4 b1 = *reinterpret_cast<const f32x4*>(lnb + k + 4);
-        wv[0] = w0.x; wv[1] = w0.y; wv[2] = w0.z; wv[3] = w0.w;
-        wv[4] = w1.x; wv[5] = w1.y; wv[6] = w1.z; wv[7] = w1.w;
-        bv[0] = b0.x; bv[1] = b0.y; bv[2] = b0.z; bv[3] = b0.w;
-        bv[4] = b1.x; bv[5] = b1.y; bv[6] = b1.z; bv[7] = b1.w;
-      }
 #pragma unroll
-      for (int rt = 0; rt < RT; ++rt) {
-        if (g.a_ln != LN_NONE) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[rt][j] = (v[rt][j] - mean[rt]) * rstd[rt] * wv[j] + bv[j];
-        }
-        if (g.a_gelu) {
-          gelu_erf8(v[rt]);
-        }
-        {
-          float xs[8];
-#pragma unroll
-          for (int j = 0; j < 8; ++j) xs[j] = kv ? v[rt][j] : 0.f;
-          split8<P>(xs, ah[rt], al[rt]);
-        }
-      }
-    }
+    for (int rt = 0; rt < RT; ++rt)
+      a_fragment<P>(v[rt], mean[rt], rstd[rt], lnw, lnb, k, kv, g.a_ln != LN_NONE, g.a_gelu != 0,
+                    ah[rt], al[rt]);
     // the A set of this slot is consumed (split) before its next load is issued, so the load
     // can reuse its registers: no loop-carried copies (and load waits) at the barrier
     afetch(min(ks + 2, ks1 - 1), an[S]);
@@ -257,17 +205,9 @@ __global__ __launch_bounds__(64 * WV) void gemm_kc_kernel(GemmArgs g) {
     for (int t = 0; t < NT; ++t) {
       const int wo = (t * 16 + l15) * KC_KP + 8 * g4;
       const bf16x8 bh = *reinterpret_cast<const bf16x8*>(Wb + wo);
-      if (SPLIT) {
-        const bf16x8 bl = *reinterpret_cast<const bf16x8*>(Wb + NC * KC_KP + wo);
+      const bf16x8 bl = SPLIT ? *reinterpret_cast<const bf16x8*>(Wb + NC * KC_KP + wo) : bh;
 #pragma unroll
-        for (int rt = 0; rt < RT; ++rt) {
-          acc[rt][t] = mma32<P>(bh, al[rt], acc[rt][t]);
-          acc[rt][t] = mma32<P>(bl, ah[rt], acc[rt][t]);
-        }
-      }
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt)
-        acc[rt][t] = mma32<P>(bh, ah[rt], acc[rt][t]);
+      for (int rt = 0; rt < RT; ++rt) acc[rt][t] = mma3<P>(acc[rt][t], bh, bl, ah[rt], al[rt]);
       if (t % 4 == 3) __builtin_amdgcn_sched_barrier(0);
     }
     wcommit(buf ^ 1, wst[S ^ 1]);  // step ks + 1's slice, fetched during step ks - 1
@@ -311,21 +251,8 @@ __global__ __launch_bounds__(64 * WV) void gemm_kc_kernel(GemmArgs g) {
     }
     float rm_ = 0.f, rs_ = 1.f, bs = 1.f;
     if (EPI == EPI_LN_GELU) {  // NC == N: the 4 lanes of a row hold the full row
-      float s = 0.f;
-#pragma unroll
-      for (int t = 0; t < NT; ++t) s += (acc[rt][t].x + acc[rt][t].y) + (acc[rt][t].z + acc[rt][t].w);
-      s = xsum16(s);
-      s = xsum32(s);
-      rm_ = s / (float)N;
-      float q = 0.f;
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        const f32x4 d = acc[rt][t] - rm_;
-        q += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
-      }
-      q = xsum16(q);
-      q = xsum32(q);
-      rs_ = rsqrtf(q / (float)N + g.e_eps);
+      rm_ = tile_sum<NT>(acc[rt]) / (float)N;
+      rs_ = rsqrtf(tile_sqdev<NT>(acc[rt], rm_) / (float)N + g.e_eps);
     } else if (EPI == EPI_RESID) {
       if (g.r_stats) {
         rm_ = g.r_stats[2 * rowc];
@@ -336,20 +263,8 @@ __global__ __launch_bounds__(64 * WV) void gemm_kc_kernel(GemmArgs g) {
       // LayerNorm partials of this row's NC stored columns (fp32 stores only: the statistics
       // are those of the stored values): {mean, M2} over the 4 lanes of the row
       if (g.o_pstats) {
-        float sm = 0.f;
-#pragma unroll
-        for (int t = 0; t < NT; ++t) sm += (acc[rt][t].x + acc[rt][t].y) + (acc[rt][t].z + acc[rt][t].w);
-        sm = xsum16(sm);
-        sm = xsum32(sm);
-        const float mu = sm * (1.f / NC);
-        float q = 0.f;
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          const f32x4 d = acc[rt][t] - mu;
-          q += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
-        }
-        q = xsum16(q);
-        q = xsum32(q);
+        const float mu = tile_sum<NT>(acc[rt]) * (1.f / NC);
+        const float q = tile_sqdev<NT>(acc[rt], mu);
         if (rv && g4 == 0)
           *reinterpret_cast<float2*>(g.o_pstats + ((int64_t)row * gridDim.y + blockIdx.y) * 2) =
               float2{mu, q};
@@ -367,27 +282,9 @@ __global__ __launch_bounds__(64 * WV) void gemm_kc_kernel(GemmArgs g) {
         v = gelu_erf4(v);
       } else if (EPI == EPI_RESID) {
         const f32x4 xr = *reinterpret_cast<const f32x4*>(g.r_x + (int64_t)rowc * N + colc);
-        if (g.r_stats) {
-          const f32x4 lw = *reinterpret_cast<const f32x4*>(g.r_ln_w + colc);
-          const f32x4 lb = *reinterpret_cast<const f32x4*>(g.r_ln_b + colc);
-          const f32x4 n2 = (xr - rm_) * rs_ * lw + lb;
-          v = xr + (n2 + v) * bs;  // attn_fused + drop_path(n2 + ffn(n2)), quirk Q4
-        } else {
-          v = xr + v * bs;
-        }
+        v = resid_epilogue(v, xr, rm_, rs_, g.r_ln_w + colc, g.r_ln_b + colc, bs, g.r_stats != nullptr);
       }
-      if (rv && col < N) {
-        if (g.out_bf16) {
-          bf16x4 o;
-          o[0] = (short)f2bf(v.x);
-          o[1] = (short)f2bf(v.y);
-          o[2] = (short)f2bf(v.z);
-          o[3] = (short)f2bf(v.w);
-          *reinterpret_cast<bf16x4*>(reinterpret_cast<uint16_t*>(g.out) + (int64_t)row * g.ldo + col) = o;
-        } else {
-          *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(g.out) + (int64_t)row * g.ldo + col) = v;
-        }
-      }
+      if (rv && col < N) store4(g.out, g.out_bf16 != 0, (int64_t)row * g.ldo, col, v);
       if (t % 2 == 1) __builtin_amdgcn_sched_barrier(0);
     }
   }
@@ -416,26 +313,14 @@ __global__ __launch_bounds__(256) void gemm_kc_reduce_kernel(GemmArgs g) {
   if (EPI == EPI_RESID) {
     const f32x4 xr = *reinterpret_cast<const f32x4*>(g.r_x + (int64_t)row * N + col);
     const float bs = g.r_scale ? g.r_scale[row / (int)g.rows_per_sample] : 1.f;
+    float rm_ = 0.f, rs_ = 1.f;
     if (g.r_stats) {
-      const float rm_ = g.r_stats[2 * row], rs_ = g.r_stats[2 * row + 1];
-      const f32x4 lw = *reinterpret_cast<const f32x4*>(g.r_ln_w + col);
-      const f32x4 lb = *reinterpret_cast<const f32x4*>(g.r_ln_b + col);
-      const f32x4 n2 = (xr - rm_) * rs_ * lw + lb;
-      v = xr + (n2 + v) * bs;  // as gemm_kc_kernel's EPI_RESID
-    } else {
-      v = xr + v * bs;
+      rm_ = g.r_stats[2 * row];
+      rs_ = g.r_stats[2 * row + 1];
     }
+    v = resid_epilogue(v, xr, rm_, rs_, g.r_ln_w + col, g.r_ln_b + col, bs, g.r_stats != nullptr);
   }
-  if (g.out_bf16) {
-    bf16x4 o;
-    o[0] = (short)f2bf(v.x);
-    o[1] = (short)f2bf(v.y);
-    o[2] = (short)f2bf(v.z);
-    o[3] = (short)f2bf(v.w);
-    *reinterpret_cast<bf16x4*>(reinterpret_cast<uint16_t*>(g.out) + (int64_t)row * g.ldo + col) = o;
-  } else {
-    *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(g.out) + (int64_t)row * g.ldo + col) = v;
-  }
+  store4(g.out, g.out_bf16 != 0, (int64_t)row * g.ldo, col, v);
 }
 
 // k splits for g (1 = none).  Only the GELU-loader fc of CCF_FFN at K >= 1536 (stage 4, 128
@@ -464,15 +349,10 @@ template <int NT, int MAP, int EPI>
 static void go_kc(const GemmArgs& g, hipStream_t s) {
   typedef KcCfg<NT> C;
   const bool split = g.prec == PREC_SPLIT;
-  void (*kern)(GemmArgs);
-  if (g.a_bf16)  // bf16 activations only exist in PREC_BF16
-    kern = gemm_kc_kernel<NT, PREC_BF16, MAP, EPI, true>;
-  else if (split)
-    kern = gemm_kc_kernel<NT, PREC_SPLIT, MAP, EPI, false>;
-  else if (g.prec == PREC_FP16)
-    kern = gemm_kc_kernel<NT, PREC_FP16, MAP, EPI, false>;
-  else
-    kern = gemm_kc_kernel<NT, PREC_BF16, MAP, EPI, false>;
+  void (*kern)(GemmArgs) = nullptr;
+  gemm_with_prec(g.prec, g.a_bf16 != 0, [&](auto P, auto ABF16) {
+    kern = gemm_kc_kernel<NT, P(), MAP, EPI, ABF16()>;
+  });
   // 16-wave workgroups for every grid of >= 1024 8-wave workgroups: stage-1 merge
   // 209.8 -> 201.9 us, stage-3 pwconv 64.2 -> 61.4, config 5 45.6-45.8 -> 46.0 volumes/s
   // (profiles/r4_gemm/)
@@ -523,9 +403,7 @@ static void dispatch_kc(int nt, const GemmArgs& g, hipStream_t s) {
 // column tiles per workgroup gemm_kc would use for g (0: it does not take the shape)
 int gemm_kc_pick_nt(const GemmArgs& g) {
   if (g.N % 32 != 0 || g.K < 8 || g.M >= ((int64_t)1 << 31)) return 0;
-  const bool known = (g.a_map == MAP_WINDOW && g.epi == EPI_STORE) ||
-                     (g.a_map == MAP_IDENTITY) || (g.a_map == MAP_MERGE && g.epi == EPI_STORE);
-  if (!known) return 0;
+  if (!gemm_known_callsite(g)) return 0;
   const int tiles = g.N / 16;
   static const int cand[] = {24, 12, 8, 6, 4, 3, 2, 1};
   // narrowest chunk the small-M search may go down to

@@ -22,7 +22,6 @@
 
 namespace wf {
 
-
 // LW_NTW column tiles per wave (N = 16 NWV LW_NTW), LW_RT row tiles of 16 rows per
 // workgroup, NWV waves: (6, 4, 4) for N = 384 (stage 2).  (3, 8) for the stage-1 N = 192
 // measured slower than gemm_rows (909 vs 974 volumes/s: K = 48 pads to two 32-wide K-steps
@@ -114,13 +113,7 @@ __global__ __launch_bounds__(NWV * 64, LnwBounds<NWV>::MINW) void gemm_lnw_kerne
     for (int t = 0; t < LW_NTW; ++t) {
       const bf16x8 bh = wh[t], bl = wl[t];
 #pragma unroll
-      for (int rt = 0; rt < LW_RT; ++rt) {
-        if (SPLIT) {
-          acc[rt][t] = mma32<P>(bh, al[rt], acc[rt][t]);
-          acc[rt][t] = mma32<P>(bl, ah[rt], acc[rt][t]);
-        }
-        acc[rt][t] = mma32<P>(bh, ah[rt], acc[rt][t]);
-      }
+      for (int rt = 0; rt < LW_RT; ++rt) acc[rt][t] = mma3<P>(acc[rt][t], bh, bl, ah[rt], al[rt]);
       // refill the PREVIOUS tile's registers with the next K-step's fragments: its MFMAs are
       // a whole tile of MFMAs old, so no load lands in a register an issued MFMA still reads
       __builtin_amdgcn_sched_barrier(0);
@@ -144,11 +137,7 @@ __global__ __launch_bounds__(NWV * 64, LnwBounds<NWV>::MINW) void gemm_lnw_kerne
   float mean[LW_RT], rstd[LW_RT];
 #pragma unroll
   for (int rt = 0; rt < LW_RT; ++rt) {
-    float s = 0.f;
-#pragma unroll
-    for (int t = 0; t < LW_NTW; ++t) s += (acc[rt][t].x + acc[rt][t].y) + (acc[rt][t].z + acc[rt][t].w);
-    s = xsum16(s);
-    s = xsum32(s);
+    const float s = tile_sum<LW_NTW>(acc[rt]);
     if (g4 == 0) red[wid][rt * 16 + l15] = s;
   }
   __syncthreads();
@@ -167,14 +156,7 @@ __global__ __launch_bounds__(NWV * 64, LnwBounds<NWV>::MINW) void gemm_lnw_kerne
   __syncthreads();  // every wave has read the sums
 #pragma unroll
   for (int rt = 0; rt < LW_RT; ++rt) {
-    float q = 0.f;
-#pragma unroll
-    for (int t = 0; t < LW_NTW; ++t) {
-      const f32x4 d = acc[rt][t] - mean[rt];
-      q += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
-    }
-    q = xsum16(q);
-    q = xsum32(q);
+    const float q = tile_sqdev<LW_NTW>(acc[rt], mean[rt]);
     if (g4 == 0) red[wid][rt * 16 + l15] = q;
   }
   __syncthreads();
@@ -193,16 +175,7 @@ __global__ __launch_bounds__(NWV * 64, LnwBounds<NWV>::MINW) void gemm_lnw_kerne
     for (int rt = 0; rt < LW_RT; ++rt) {
       const int64_t row = r0 + rt * 16 + l15;
       const f32x4 v = gelu_half4((acc[rt][t] - mean[rt]) * rstd[rt] * lw + lb);
-      if (row < M) {
-        if (g.out_bf16) {
-          bf16x4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = (short)f2bf(v[e]);
-          *reinterpret_cast<bf16x4*>(reinterpret_cast<uint16_t*>(g.out) + row * g.ldo + col) = o;
-        } else {
-          *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(g.out) + row * g.ldo + col) = v;
-        }
-      }
+      if (row < M) store4(g.out, g.out_bf16 != 0, row * g.ldo, col, v);
     }
   }
 }
@@ -210,10 +183,9 @@ __global__ __launch_bounds__(NWV * 64, LnwBounds<NWV>::MINW) void gemm_lnw_kerne
 template <int KS, int NTW, int RT, int NWV = 4>
 void go_lnw(const GemmArgs& g, hipStream_t s) {
   const dim3 grid((unsigned)cdiv(g.M, RT * 16));
-  auto k = g.prec == PREC_SPLIT  ? gemm_lnw_kernel<PREC_SPLIT, KS, NTW, RT, NWV>
-           : g.prec == PREC_FP16 ? gemm_lnw_kernel<PREC_FP16, KS, NTW, RT, NWV>
-                                 : gemm_lnw_kernel<PREC_BF16, KS, NTW, RT, NWV>;
-  hipLaunchKernelGGL(k, grid, dim3(NWV * 64), 0, s, g);
+  gemm_with_prec(g.prec, false, [&](auto P, auto) {  // fp32 rows only (try_launch_gemm_lnw)
+    hipLaunchKernelGGL((gemm_lnw_kernel<P(), KS, NTW, RT, NWV>), grid, dim3(NWV * 64), 0, s, g);
+  });
 }
 
 // the wide-row shapes this kernel takes: the stage-3 pwconv N = 768 (K <= 192) -- 78.7 us

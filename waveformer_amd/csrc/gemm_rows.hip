@@ -17,14 +17,6 @@
 // (identity / window gather / PatchMerging gather) and the epilogue are template parameters
 // so each call site compiles to straight-line code with 32-bit index math.
 #include "gemm_common.hpp"
-// cache policy of the staged (1-KB-per-instruction) output stores: 0 default, 2 nt (A/B)
-#ifndef WF_ROWS_STORE_POLICY
-#define WF_ROWS_STORE_POLICY 0
-#endif
-
-#ifndef WF_ROWS_DBG  // 1: timing-experiment build (GemmArgs::dbg phase skips; never the shipped library)
-#define WF_ROWS_DBG 0
-#endif
 
 namespace wf {
 
@@ -139,59 +131,24 @@ __global__ __launch_bounds__(NTH) void gemm_rows_kernel(GemmArgs g) {
     const RowMapper<MAP> rmn(g, arow_n);
     float mean = gmean, rstd = grstd;
     if (a_ln == LN_COMPUTE) {  // lanes l15, l15+16, l15+32, l15+48 share the row
-      // two passes, each issuing its loads four octets at a time (a load per iteration waited
-      // out one latency per octet); same summation order, clamped tail octets add 0
+      // two passes over the row (ln_row_batches: four octets per batch)
       const int noct = K / 8;
+      const auto off = [&](int k) { return rm.offset(g, k); };
       float s = 0.f;
-      for (int cb = g4; cb < noct; cb += 16) {
-        float v[4][8];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) load8f<ABF16>(g.a_src, rm.offset(g, min(cb + 4 * u, noct - 1) * 8), v[u]);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const float mk = cb + 4 * u < noct ? 1.f : 0.f;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) s += v[u][j] * mk;
-        }
-      }
+      ln_row_batches<ABF16>(g.a_src, noct, g4, off, [&](float x, float mk) { s += x * mk; });
       s = xsum16(s);
       s = xsum32(s);
       mean = s / (float)K;
       float q = 0.f;
-      for (int cb = g4; cb < noct; cb += 16) {
-        float v[4][8];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) load8f<ABF16>(g.a_src, rm.offset(g, min(cb + 4 * u, noct - 1) * 8), v[u]);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const float mk = cb + 4 * u < noct ? 1.f : 0.f;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const float d = (v[u][j] - mean) * mk;
-            q += d * d;
-          }
-        }
-      }
+      ln_row_batches<ABF16>(g.a_src, noct, g4, off, [&](float x, float mk) {
+        const float d = (x - mean) * mk;
+        q += d * d;
+      });
       q = xsum16(q);
       q = xsum32(q);
       rstd = rsqrtf(q / (float)K + g.a_eps);
     } else if (a_ln == LN_PARTIAL) {  // combine the producer's per-group {mean, M2}
-      const int np = g.a_np;
-      const float* ps = g.a_stats + (int64_t)arow_c * np * 2;
-      float s = 0.f;
-      for (int c = g4; c < np; c += 4) s += ps[2 * c];
-      s = xsum16(s);
-      s = xsum32(s);
-      mean = s / (float)np;
-      const float ng = (float)(K / np);
-      float q = 0.f;
-      for (int c = g4; c < np; c += 4) {
-        const float d = ps[2 * c] - mean;
-        q += ps[2 * c + 1] + ng * d * d;
-      }
-      q = xsum16(q);
-      q = xsum32(q);
-      rstd = rsqrtf(q / (float)K + g.a_eps);
+      ln_partial_combine(g.a_stats + (int64_t)arow_c * g.a_np * 2, g.a_np, K, g.a_eps, g4, mean, rstd);
     }
 
     f32x4 acc[NT];
@@ -199,9 +156,12 @@ __global__ __launch_bounds__(NTH) void gemm_rows_kernel(GemmArgs g) {
     for (int t = 0; t < NT; ++t) acc[t] = f32x4{0, 0, 0, 0};
 
     // one 32-deep k step on the A fragment v (LayerNorm / GELU / split in the loader)
-    auto kstep = [&](int k0, float* v) {
+    auto kstep = [&](int k0, float (&v)[8]) {
       const int k = k0 + 8 * g4;
       const bool kv = k < K;
+      // a_fragment's text, inline: through the helper the store kernels of this file allocate
+      // other registers and <9, SPLIT, window> / <6, SPLIT, identity> measured 3-6 % slower
+      // 
       if (a_ln != LN_NONE) {
         const f32x4 w0 = *reinterpret_cast<const f32x4*>(lnw + k);
         const f32x4 w1 = *reinterpret_cast<const f32x4*>(lnw + k + 4);
@@ -229,12 +189,8 @@ __global__ __launch_bounds__(NTH) void gemm_rows_kernel(GemmArgs g) {
       for (int t = 0; t < NT; ++t) {
         const int wo = (t * 16 + l15) * KP + k0 + 8 * g4;
         const bf16x8 bh = *reinterpret_cast<const bf16x8*>(Wl + wo);
-        if (SPLIT) {
-          const bf16x8 bl = *reinterpret_cast<const bf16x8*>(Wl + NCOL * KP + wo);
-          acc[t] = mma32<P>(bh, al, acc[t]);
-          acc[t] = mma32<P>(bl, ah, acc[t]);
-        }
-        acc[t] = mma32<P>(bh, ah, acc[t]);
+        const bf16x8 bl = SPLIT ? *reinterpret_cast<const bf16x8*>(Wl + NCOL * KP + wo) : bh;
+        acc[t] = mma3<P>(acc[t], bh, bl, ah, al);
         // keep the LDS fragment reads from being hoisted all at once (VGPR pressure ->
         // occupancy): a scheduling fence every 3 tiles
         if (t % 3 == 2) __builtin_amdgcn_sched_barrier(0);
@@ -254,14 +210,8 @@ __global__ __launch_bounds__(NTH) void gemm_rows_kernel(GemmArgs g) {
         gmean = g.a_stats[2 * arow_n];
         grstd = g.a_stats[2 * arow_n + 1];
       }
-#if WF_ROWS_DBG
-      if (!(g.dbg & 4)) {
-#endif
       kstep(0, v0);
       if (K32 > 32) kstep(32, v1);
-#if WF_ROWS_DBG
-      }
-#endif
     } else {
       // k loop with a one-step register prefetch of the A fragment (last step: the next tile's)
 #pragma unroll 1
@@ -331,11 +281,7 @@ __global__ __launch_bounds__(NTH) void gemm_rows_kernel(GemmArgs g) {
       const int col = c0 + t * 16 + 4 * g4;
       const int colc = min(col, N - 4);
       f32x4 v = acc[t];
-#if WF_ROWS_DBG
-      if (EPI == EPI_LN_GELU && !(g.dbg & 2)) {
-#else
       if (EPI == EPI_LN_GELU) {
-#endif
         // elw / elb hold HALF the LayerNorm affine (staged x 0.5, exact): the normalised
         // value comes out as GELU's half input; (v - mean) * rstd as one FMA per pair
         const f32x4 lw = *reinterpret_cast<const f32x4*>(elw + t * 16 + 4 * g4);
@@ -347,14 +293,7 @@ __global__ __launch_bounds__(NTH) void gemm_rows_kernel(GemmArgs g) {
         v = f32x4{h0.x, h0.y, h1.x, h1.y};
       } else if (EPI == EPI_RESID) {
         const f32x4 xr = *reinterpret_cast<const f32x4*>(g.r_x + (int64_t)rowc * N + colc);
-        if (g.r_stats) {
-          const f32x4 lw = *reinterpret_cast<const f32x4*>(g.r_ln_w + colc);
-          const f32x4 lb = *reinterpret_cast<const f32x4*>(g.r_ln_b + colc);
-          const f32x4 n2 = (xr - rm_) * rs_ * lw + lb;
-          v = xr + (n2 + v) * bs;  // attn_fused + drop_path(n2 + ffn(n2)), quirk Q4
-        } else {
-          v = xr + v * bs;         // bare CCF_FFN.forward: x + x_out
-        }
+        v = resid_epilogue(v, xr, rm_, rs_, g.r_ln_w + colc, g.r_ln_b + colc, bs, g.r_stats != nullptr);
       }
       // LN+GELU (CCF_FFN pwconv): the chunk is the whole row and the storage type follows
       // the precision, so the store needs no column test and no runtime type branch
@@ -364,12 +303,7 @@ __global__ __launch_bounds__(NTH) void gemm_rows_kernel(GemmArgs g) {
         // range-checked buffer store (rows >= M dropped by the descriptor): no exec branch,
         // so the compiler can count these stores and wait for the next tile's loads only
         if (obf) {
-          bf16x4 o;
-          o[0] = (short)f2bf(v.x);
-          o[1] = (short)f2bf(v.y);
-          o[2] = (short)f2bf(v.z);
-          o[3] = (short)f2bf(v.w);
-          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), orsrc,
+          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, pack_bf16x4(v)), orsrc,
                                                 (int)((row * g.ldo + col) * 2), 0, 0);
         } else if (STAGE) {
           if constexpr (SROWS == 16)
@@ -385,16 +319,7 @@ __global__ __launch_bounds__(NTH) void gemm_rows_kernel(GemmArgs g) {
           *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(g.out) +
                                     (sv_p0 + sv_off[t]) * g.ldo + sv_col[t]) = v;
       } else if (rv && cv) {
-        if (obf) {
-          bf16x4 o;
-          o[0] = (short)f2bf(v.x);
-          o[1] = (short)f2bf(v.y);
-          o[2] = (short)f2bf(v.z);
-          o[3] = (short)f2bf(v.w);
-          *reinterpret_cast<bf16x4*>(reinterpret_cast<uint16_t*>(g.out) + (int64_t)row * g.ldo + col) = o;
-        } else {
-          *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(g.out) + (int64_t)row * g.ldo + col) = v;
-        }
+        store4(g.out, obf, (int64_t)row * g.ldo, col, v);
       }
       if (t % 2 == 1) __builtin_amdgcn_sched_barrier(0);  // bound load hoisting (VGPRs)
     }
@@ -418,15 +343,9 @@ __global__ __launch_bounds__(NTH) void gemm_rows_kernel(GemmArgs g) {
         for (int j = 0; j < SROWS * RC / 64; ++j) {
           const int c = j * 64 + lane, r = c / RC, c4 = c - r * RC;
           const f32x4 v = *reinterpret_cast<const f32x4*>(ostg + r * OST + 4 * c4);
-#if WF_ROWS_DBG
-          const int doff = (g.dbg & 1) ? 0x7fffff00 : 0;  // past the descriptor: dropped
-#else
-          constexpr int doff = 0;
-#endif
           __builtin_amdgcn_raw_buffer_store_b128(
               __builtin_bit_cast(u32x4, v), orsrc,
-              doff + (int)(((tile * 16 + half * SROWS + r) * g.ldo + 4 * c4) * 4), 0,
-              WF_ROWS_STORE_POLICY);
+              (int)(((tile * 16 + half * SROWS + r) * g.ldo + 4 * c4) * 4), 0, 0);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -445,33 +364,30 @@ static bool rows_w12(const GemmArgs& g) {
 }
 
 template <int NT, int MAP, int EPI>
-static void go_rows(const GemmArgs& g0, dim3 grid, size_t lds, hipStream_t s) {
-  GemmArgs g = g0;
-  g.dbg = WF_ROWS_DBG && getenv("WF_ROWS_DBG") ? atoi(getenv("WF_ROWS_DBG")) : 0;
-  void (*kern)(GemmArgs);
+static void go_rows(const GemmArgs& g, dim3 grid, size_t lds, hipStream_t s) {
+  auto launch = [&](void (*kern)(GemmArgs)) {
+    if (lds > 64 * 1024)
+      set_max_lds(reinterpret_cast<const void*>(kern), (int)lds);
+    hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, g);
+  };
   if constexpr (EPI == EPI_LN_GELU && MAP == MAP_IDENTITY) {
     if (rows_w12(g)) {  // lds already holds the 12 x 8-row output staging (host below)
-      kern = g.prec == PREC_SPLIT ? gemm_rows_kernel<NT, PREC_SPLIT, MAP, EPI, false, 768>
-                                  : gemm_rows_kernel<NT, PREC_FP16, MAP, EPI, false, 768>;
+      void (*kern)(GemmArgs) = g.prec == PREC_SPLIT
+                                   ? gemm_rows_kernel<NT, PREC_SPLIT, MAP, EPI, false, 768>
+                                   : gemm_rows_kernel<NT, PREC_FP16, MAP, EPI, false, 768>;
       set_max_lds(reinterpret_cast<const void*>(kern), (int)lds);
       const unsigned gx = (unsigned)std::min<int64_t>(cdiv((g.M + 15) / 16, 12), 256);
       hipLaunchKernelGGL(kern, dim3(gx, grid.y), dim3(768), lds, s, g);
       return;
     }
     // bf16 storage (PREC_BF16; bf16 activations only exist there)
-    kern = g.a_bf16 ? gemm_rows_kernel<NT, PREC_BF16, MAP, EPI, true>
-                    : gemm_rows_kernel<NT, PREC_BF16, MAP, EPI, false>;
-  } else if (g.a_bf16)  // bf16 activations only exist in PREC_BF16
-    kern = gemm_rows_kernel<NT, PREC_BF16, MAP, EPI, true>;
-  else if (g.prec == PREC_SPLIT)
-    kern = gemm_rows_kernel<NT, PREC_SPLIT, MAP, EPI, false>;
-  else if (g.prec == PREC_FP16)
-    kern = gemm_rows_kernel<NT, PREC_FP16, MAP, EPI, false>;
-  else
-    kern = gemm_rows_kernel<NT, PREC_BF16, MAP, EPI, false>;
-  if (lds > 64 * 1024)
-    set_max_lds(reinterpret_cast<const void*>(kern), (int)lds);
-  hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, g);
+    launch(g.a_bf16 ? gemm_rows_kernel<NT, PREC_BF16, MAP, EPI, true>
+                    : gemm_rows_kernel<NT, PREC_BF16, MAP, EPI, false>);
+  } else {
+    gemm_with_prec(g.prec, g.a_bf16 != 0, [&](auto P, auto ABF16) {
+      launch(gemm_rows_kernel<NT, P(), MAP, EPI, ABF16()>);
+    });
+  }
 }
 
 template <int MAP, int EPI>
@@ -490,11 +406,7 @@ static void dispatch_nt(int nt, const GemmArgs& g, dim3 grid, size_t lds, hipStr
 
 int try_launch_gemm_rows(const GemmArgs& g, hipStream_t s, bool single_chunk_only) {
   if (g.N % 16 != 0 || g.K < 8 || g.M >= ((int64_t)1 << 31)) return 0;
-  // call-site shapes (the others fall back to gemm_ares): window qkv, identity store/LN/resid,
-  // PatchMerging gather
-  const bool known = (g.a_map == MAP_WINDOW && g.epi == EPI_STORE) ||
-                     (g.a_map == MAP_IDENTITY) || (g.a_map == MAP_MERGE && g.epi == EPI_STORE);
-  if (!known) return 0;
+  if (!gemm_known_callsite(g)) return 0;
   // the LN+GELU instantiations are specialised to the CCF_FFN pwconv's loader and storage
   const int64_t out_bytes = g.M * g.ldo * ((g.prec == PREC_BF16 || g.a_bf16) ? 2 : 4);
   if (g.epi == EPI_LN_GELU && (g.K > 64 || out_bytes >= ((int64_t)1 << 31) || (g.a_ln != LN_GIVEN && g.a_ln != LN_NONE) || g.a_gelu ||

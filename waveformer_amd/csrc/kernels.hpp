@@ -43,6 +43,20 @@ __device__ __forceinline__ f32x4 mma16(bf16x4 a, bf16x4 b, f32x4 c) {  // 16x16x
                                                  __builtin_bit_cast(f16x4, b), c, 0, 0, 0);
   else return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0);
 }
+// One k step of a 16x16x32 product: fragment pair w (the MFMA's A operand) against fragment
+// pair a (its B operand).  For PREC_SPLIT the three products go hi * lo, lo * hi, hi * hi IN
+// THIS ORDER -- the order is what makes the outputs bit-stable across the kernels that share a
+// shape; the other modes have the one product (the lo fragments are then unused, their loads
+// dead).  Callers keep their own operand-load order in front of it.
+template <int P>
+__device__ __forceinline__ f32x4 mma3(f32x4 acc, const bf16x8& w_hi, const bf16x8& w_lo,
+                                      const bf16x8& a_hi, const bf16x8& a_lo) {
+  if constexpr (P == PREC_SPLIT) {
+    acc = mma32<P>(w_hi, a_lo, acc);
+    acc = mma32<P>(w_lo, a_hi, acc);
+  }
+  return mma32<P>(w_hi, a_hi, acc);
+}
 // The operand words of a pair of values (first value in the low half): hi = op_cvt, lo = the
 // split's lo part (PREC_SPLIT) or 0.  For PREC_SPLIT, y - hi comes from v_dot2c_f32_bf16 of the
 // packed hi pair against (-1, 0) / (0, -1) accumulated onto y -- one VALU op per value instead
@@ -139,7 +153,6 @@ struct GemmArgs {
   const float* r_ln_b;
   const float* r_scale;  //   per-sample factor on the added branch (DropPath) or NULL
   int64_t rows_per_sample; // M / B for r_scale
-  int dbg;               // timing experiments only (builds with WF_ROWS_DBG=1): phases skipped
   float* o_pstats;       // EPI_STORE (gemm_kc): if non-NULL, per (row, column chunk) {mean, M2}
                          //   of the stored values, (M, N / chunk, 2) -- LN statistics partials
   float* kpart;          // gemm_kc split-K scratch (caller-owned, kpart_bytes), or NULL: small

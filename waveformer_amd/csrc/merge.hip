@@ -27,10 +27,9 @@ constexpr int MR_N = 2 * MR_C;                // 96
 constexpr int MR_NT = MR_N / 16;              // 6 column tiles
 constexpr int MR_KS = MR_K / 32;              // 12 k steps
 constexpr int MR_KP = MR_K + WF_LDS_KPAD;     // LDS row stride in bf16: 200 dwords, 8 mod 16
-#ifndef WF_MR_WAVES  // waves per merge_res workgroup: 8 measured 135.5-139.3 us against 141.8-143.8
-#define WF_MR_WAVES 8  // (12), 149.9-151.0 (6), 154.8-155.6 (4); 16 spills (r6/r6ap_merge_res_waves_ab.txt)
-#endif
-constexpr int MR_WAVES = WF_MR_WAVES;
+// waves per merge_res workgroup: 8 measured 135.5-139.3 us against 141.8-143.8 (12),
+// 149.9-151.0 (6), 154.8-155.6 (4); 16 spills (r6/r6ap_merge_res_waves_ab.txt)
+constexpr int MR_WAVES = 8;
 
 template <int P>
 __global__ __launch_bounds__(64 * MR_WAVES, 1) void merge_res_kernel(GemmArgs g) {
@@ -127,35 +126,16 @@ __global__ __launch_bounds__(64 * MR_WAVES, 1) void merge_res_kernel(GemmArgs g)
 #pragma unroll
     for (int ks = 0; ks < MR_KS; ++ks) {
       __builtin_amdgcn_sched_barrier(0);
-      const f32x4 w0 = *reinterpret_cast<const f32x4*>(Lw + ks * 128);
-      const f32x4 w1 = *reinterpret_cast<const f32x4*>(Lw + ks * 128 + 16);
-      const f32x4 b0 = *reinterpret_cast<const f32x4*>(Lb + ks * 128);
-      const f32x4 b1 = *reinterpret_cast<const f32x4*>(Lb + ks * 128 + 16);
-      const float wv[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
-      const float bv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+      // gemm_kc's transform (every k < K here); Lw / Lb + 128 ks bytes fold into the ds_read offsets
       bf16x8 ah, al;
-      {
-        float xs[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float xv = (a[ks][j] - mean) * rstd * wv[j] + bv[j];
-          // fp16: the fp32 value first (gemm_kc's double rounding), not a v_fma_mix straight
-          // to fp16, so the two paths stay bit-identical
-          if (!SPLIT) asm volatile("" : "+v"(xv));
-          xs[j] = xv;
-        }
-        split8<P>(xs, ah, al);
-      }
+      a_fragment<P>(a[ks], mean, rstd, reinterpret_cast<const float*>(Lw),
+                    reinterpret_cast<const float*>(Lb), ks * 32, true, true, false, ah, al);
 #pragma unroll
       for (int t = 0; t < MR_NT; ++t) {
         const int wo = (t * 16 * MR_KP + ks * 32) * 2;
         const bf16x8 bh = *reinterpret_cast<const bf16x8*>(Wb + wo);
-        if (SPLIT) {
-          const bf16x8 bl = *reinterpret_cast<const bf16x8*>(Wb + MR_N * MR_KP * 2 + wo);
-          acc[t] = mma32<P>(bh, al, acc[t]);
-          acc[t] = mma32<P>(bl, ah, acc[t]);
-        }
-        acc[t] = mma32<P>(bh, ah, acc[t]);
+        const bf16x8 bl = SPLIT ? *reinterpret_cast<const bf16x8*>(Wb + MR_N * MR_KP * 2 + wo) : bh;
+        acc[t] = mma3<P>(acc[t], bh, bl, ah, al);
         // bound the hoisting of the weight-fragment reads (VGPRs: three waves per SIMD)
         if (t % 3 == 2) __builtin_amdgcn_sched_barrier(0);
       }

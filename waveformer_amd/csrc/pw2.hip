@@ -138,12 +138,8 @@ __global__ __launch_bounds__(64 * NW, 1) void pw2_res_kernel(GemmArgs g) {
       for (int t = 0; t < NT; ++t) {
         const int wo = t * 16 * RB + 64 * ks;
         const bf16x8 bh = *reinterpret_cast<const bf16x8*>(Wb + wo);
-        if (SPLIT) {
-          const bf16x8 bl = *reinterpret_cast<const bf16x8*>(Wb + PLANE + wo);
-          acc[t] = mma32<P>(bh, al[ks], acc[t]);
-          acc[t] = mma32<P>(bl, ah[ks], acc[t]);
-        }
-        acc[t] = mma32<P>(bh, ah[ks], acc[t]);
+        const bf16x8 bl = SPLIT ? *reinterpret_cast<const bf16x8*>(Wb + PLANE + wo) : bh;
+        acc[t] = mma3<P>(acc[t], bh, bl, ah[ks], al[ks]);
         if (t % 4 == 3) __builtin_amdgcn_sched_barrier(0);  // bound the fragment-read hoisting
       }
     }
@@ -155,27 +151,12 @@ __global__ __launch_bounds__(64 * NW, 1) void pw2_res_kernel(GemmArgs g) {
     // each reduced over the row's 4 lanes, then a fixed tree
     float part[8];
 #pragma unroll
-    for (int w = 0; w < 8; ++w) {
-      float s = 0.f;
-#pragma unroll
-      for (int t = 3 * w; t < 3 * w + 3; ++t) s += (acc[t].x + acc[t].y) + (acc[t].z + acc[t].w);
-      s = xsum16(s);
-      part[w] = xsum32(s);
-    }
+    for (int w = 0; w < 8; ++w) part[w] = tile_sum<3>(acc + 3 * w);
     const float mean =
         (((part[0] + part[1]) + (part[2] + part[3])) + ((part[4] + part[5]) + (part[6] + part[7]))) *
         (1.f / N);
 #pragma unroll
-    for (int w = 0; w < 8; ++w) {
-      float q = 0.f;
-#pragma unroll
-      for (int t = 3 * w; t < 3 * w + 3; ++t) {
-        const f32x4 d = acc[t] - mean;
-        q += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
-      }
-      q = xsum16(q);
-      part[w] = xsum32(q);
-    }
+    for (int w = 0; w < 8; ++w) part[w] = tile_sqdev<3>(acc + 3 * w, mean);
     const float rstd = rsqrtf(
         (((part[0] + part[1]) + (part[2] + part[3])) + ((part[4] + part[5]) + (part[6] + part[7]))) *
             (1.f / N) + g.e_eps);
