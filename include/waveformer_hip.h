@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define WF_ABI_VERSION 18
+#define WF_ABI_VERSION 19
 
 enum { WF_PREC_BF16 = 0, WF_PREC_BF16X3 = 1, WF_PREC_FP16 = 2 };
 
@@ -194,6 +194,32 @@ int wf_idwt3d_level(const float* const* coef, const int64_t* coef_strides, int64
                     int64_t n_z, int64_t n_y, int64_t n_x, const float* rec_lo,
                     const float* rec_hi, int taps, float* out, int64_t out_bstride,
                     int64_t out_cstride, void* stream);
+
+/* The backward of the two entries above (ABI 19): training through ptwt.wavedec3 / waverec3
+ * with db1..db4.  Same fp32 arithmetic forms as the forward, applied to the cotangent.
+ *
+ * wf_dwt3d_bwd: the adjoint of one analysis level.  gbands: the 8 band gradients, contiguous
+ * (8, P, d, h, w) as wf_dwt3d_fwd writes them, d = (D + taps - 1) / 2.  dx: P contiguous
+ * (D, H, W) planes, every element written; D, H, W are the forward's input sizes (odd sizes
+ * allowed).  dec_lo / dec_hi: HOST arrays, the same arguments as wf_dwt3d_fwd.
+ *   dx[o] = sum_{j == t (mod 2)} dec[taps-1-j] * g[(t - j) / 2],  t = o + taps - 2, per axis. */
+int wf_dwt3d_bwd(const float* gbands, float* dx, int64_t P, int64_t D, int64_t H, int64_t W,
+                 const float* dec_lo, const float* dec_hi, int taps, void* stream);
+
+/* wf_idwt3d_level_bwd: the adjoint of one synthesis level.  gout: the gradient of the level's
+ * output (B, C, Oz, Oy, Ox), O = 2n - taps + 2; its (z, y, x) block is contiguous, element
+ * (b, c, z, y, x) at b*gout_bstride + c*gout_cstride + (z*Oy + y)*Ox + x (e.g. the first C
+ * channels of the gradient of torch.cat((out, skip), 1)).  gcoef[8]: the coefficient
+ * gradients, band k as above (gcoef[0] = LL), each written through its own 5 element strides
+ * gcoef_strides[5k .. 5k+4] = (b, c, z, y, x); bands 1..7 are (B, C, n_z, n_y, n_x), band 0 is
+ * (B, C, n_z + extra_z, n_y + extra_y, n_x + extra_x) with extra_* in {0, 1}: the LL samples
+ * wf_idwt3d_level's caller cropped get gradient 0.  rec_lo / rec_hi: HOST arrays.
+ *   gc[m] = sum_j rec[j] * gout[2m + j - (taps - 2)],  m < n, per axis.                       */
+int wf_idwt3d_level_bwd(const float* gout, int64_t gout_bstride, int64_t gout_cstride, int64_t B,
+                        int64_t C, int64_t n_z, int64_t n_y, int64_t n_x, int extra_z,
+                        int extra_y, int extra_x, const float* rec_lo, const float* rec_hi,
+                        int taps, float* const* gcoef, const int64_t* gcoef_strides,
+                        void* stream);
 
 /* ---- decoder: 3x3x3 convolution ------------------------------------- */
 /* Replaces the decoder's Conv3d(Cin, Cout, 3, stride 1, padding 1) of MONAI's Convolution /

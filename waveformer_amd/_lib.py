@@ -57,6 +57,9 @@ SIGNATURES = {
     "wf_dwt3d_fwd": (_I, [_P, _P, _I64, _I64, _I64, _I64, _P, _P, _I, _P]),
     "wf_idwt3d_level": (_I, [_P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _I, _P, _I64, _I64,
                              _P]),
+    "wf_dwt3d_bwd": (_I, [_P, _P, _I64, _I64, _I64, _I64, _P, _P, _I, _P]),
+    "wf_idwt3d_level_bwd": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I, _I, _I, _P,
+                                 _P, _I, _P, _P, _P]),
     "wf_conv3d_k3_packed_elems": (_I64, [_I64, _I64]),
     "wf_conv3d_k3_pack": (_I, [_P, _P, _I64, _I64, _P]),
     "wf_conv3d_k3_pack_f16": (_I, [_P, _P, _I64, _I64, _P]),
@@ -135,7 +138,7 @@ SIGNATURES = {
     "wf_transpose_cs": (_I, [_P, _P, _I64, _I64, _I64, _P]),
 }
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 _lock = threading.Lock()
 _lib = None
 _err = None

@@ -118,6 +118,35 @@ def idwt3d_haar(ll: torch.Tensor, details: Sequence[Dict[str, torch.Tensor]]) ->
     return torch.ops.waveformer.idwt3d(ll, [dct[k] for dct in details for k in DETAIL_KEYS])
 
 
+def wavedec3(x: torch.Tensor, wavelet, level: int) -> List:
+    """Differentiable ptwt.wavedec3(x, wavelet, mode='zero', level=level) for db1..db4 ->
+    [LL, dict_coarsest, ..., dict_finest]: a chain of waveformer::wavedec3_level."""
+    from . import library  # noqa: F401
+    if level < 1:
+        raise ValueError("wavedec3: level must be >= 1")
+    name = ops.wavelet_name(wavelet)
+    dets = []
+    cur = x
+    for _ in range(level):
+        bands = torch.ops.waveformer.wavedec3_level(cur, name).unbind(0)  # one stack in backward
+        dets.append(dict(zip(DETAIL_KEYS, bands[1:])))
+        cur = bands[0]
+    return [cur] + dets[::-1]
+
+
+def waverec3(coeffs: Sequence, wavelet) -> torch.Tensor:
+    """Differentiable ptwt.waverec3((LL, dict_coarsest, ..., dict_finest), wavelet) for
+    db1..db4: a chain of waveformer::waverec3_level."""
+    from . import library  # noqa: F401
+    if len(coeffs) < 2:
+        raise ValueError("waverec3: need at least one detail level")
+    name = ops.wavelet_name(wavelet)
+    x = coeffs[0]
+    for det in coeffs[1:]:
+        x = torch.ops.waveformer.waverec3_level(x, [det[k] for k in DETAIL_KEYS], name)
+    return x
+
+
 # ------------------------------------------------------------------------------------------
 # a10: PatchEmbed and proj_out
 # ------------------------------------------------------------------------------------------

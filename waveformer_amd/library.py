@@ -7,6 +7,8 @@ them (attention.py:83-104, wave_helper.py:349 / :470-512, idwt_upsample.py:160).
 
   waveformer::dwt3d          ptwt.wavedec3(level=1, 'db1') of a channel-last volume (+ norm1)
   waveformer::idwt3d         ptwt.waverec3(..., 'db1'), 1..4 levels
+  waveformer::wavedec3_level one level of ptwt.wavedec3 of an NCDHW volume, db1..db4, any sizes
+  waveformer::waverec3_level one level of ptwt.waverec3, db1..db4 (strided coefficients)
   waveformer::window_attn    window_partition + Attention.forward + the Q1 reshape-reverse
   waveformer::msfuse         the multi-scale trilinear fuse + shortcut (+ norm2 statistics)
   waveformer::ccf_ffn        norm2 + CCF_FFN + the Q4 double residual
@@ -186,6 +188,113 @@ def _idwt3d_bwd(ctx, gout):
 
 
 idwt3d.register_autograd(_idwt3d_bwd, setup_context=_idwt3d_setup)
+
+
+# ------------------------------------------------------------------------------------------
+# C5: one level of a general orthogonal wavelet (db1..db4, NCDHW, any sizes); a multi-level
+# transform is a chain of these (autograd.wavedec3 / waverec3)
+# ------------------------------------------------------------------------------------------
+@torch.library.custom_op("waveformer::wavedec3_level", mutates_args=(), device_types="cuda")
+def wavedec3_level(x: Tensor, wavelet: str) -> Tensor:
+    """One level of ptwt.wavedec3(x, wavelet, mode='zero'): x (B, C, D, H, W) -> bands
+    (8, B, C, d, h, w), d = (D + L - 1) // 2; band 0 = LL, 1..7 = DETAIL_KEYS."""
+    return ops.dwt3d(x, wavelet)
+
+
+@wavedec3_level.register_fake
+def _(x, wavelet):
+    L = ops.wavelet_taps(wavelet)
+    B, C, D, H, W = x.shape
+    return x.new_empty((8, B, C, (D + L - 1) // 2, (H + L - 1) // 2, (W + L - 1) // 2))
+
+
+def _wavedec3_setup(ctx, inputs, output):
+    x, wavelet = inputs
+    ctx.size = tuple(x.shape[2:])
+    ctx.wavelet = wavelet
+
+
+@torch.library.custom_op("waveformer::wavedec3_level_backward", mutates_args=(),
+                         device_types="cuda")
+def wavedec3_level_backward(gbands: Tensor, size: List[int], wavelet: str) -> Tensor:
+    """dx (B, C) + size of wavedec3_level: the synthesis form with the analysis taps over the
+    band gradients, kept for the input's extent (wf_dwt3d_bwd)."""
+    return ops.dwt3d_bwd(gbands, size, wavelet)
+
+
+@wavedec3_level_backward.register_fake
+def _(gbands, size, wavelet):
+    return gbands.new_empty((gbands.shape[1], gbands.shape[2]) + tuple(size))
+
+
+def _wavedec3_bwd(ctx, gbands):
+    return torch.ops.waveformer.wavedec3_level_backward(gbands, list(ctx.size),
+                                                        ctx.wavelet), None
+
+
+wavedec3_level.register_autograd(_wavedec3_bwd, setup_context=_wavedec3_setup)
+
+
+@torch.library.custom_op("waveformer::waverec3_level", mutates_args=(), device_types="cuda")
+def waverec3_level(ll: Tensor, details: List[Tensor], wavelet: str) -> Tensor:
+    """One level of ptwt.waverec3((ll, details), wavelet): the 7 details (DETAIL_KEYS order)
+    (B, C, n_z, n_y, n_x) of any strides, ll the same or one sample longer per axis (cropped,
+    pywt's rule) -> (B, C, 2n - L + 2 per axis)."""
+    if len(details) != 7:
+        raise ValueError(f"waverec3_level: expected 7 details, got {len(details)}")
+    return ops.waverec3([ll, dict(zip(DETAIL_KEYS, details))], wavelet)
+
+
+@waverec3_level.register_fake
+def _(ll, details, wavelet):
+    L = ops.wavelet_taps(wavelet)
+    B, C, nz, ny, nx = details[0].shape
+    return ll.new_empty((B, C, 2 * nz - L + 2, 2 * ny - L + 2, 2 * nx - L + 2))
+
+
+def _is_cl(t: Tensor) -> bool:
+    """NCDHW-shaped with channel-last strides (a band view of the encoder's buffers)."""
+    return t.shape[1] > 1 and t.stride(1) == 1 and not t.is_contiguous()
+
+
+def _waverec3_setup(ctx, inputs, output):
+    ll, details, wavelet = inputs
+    ctx.ll_size = tuple(ll.shape[2:])
+    # each gradient in its input's layout
+    ctx.cl = [_is_cl(t) for t in [ll] + list(details)]
+    ctx.wavelet = wavelet
+
+
+@torch.library.custom_op("waveformer::waverec3_level_backward", mutates_args=(),
+                         device_types="cuda")
+def waverec3_level_backward(gout: Tensor, ll_size: List[int], channel_last: List[bool],
+                            wavelet: str) -> List[Tensor]:
+    """[d ll] + the 7 detail gradients of waverec3_level: the analysis form with the synthesis
+    taps over the output gradient (wf_idwt3d_level_bwd); 8 separate tensors (op outputs may not
+    alias), gradient k channel-last strided where channel_last[k]."""
+    return ops.idwt3d_level_bwd(gout, ll_size, wavelet, channel_last)
+
+
+@waverec3_level_backward.register_fake
+def _(gout, ll_size, channel_last, wavelet):
+    L = ops.wavelet_taps(wavelet)
+    B, C = gout.shape[:2]
+    n = tuple((o + L - 2) // 2 for o in gout.shape[2:])
+    out = []
+    for k in range(8):
+        shp = tuple(ll_size) if k == 0 else n
+        out.append(gout.new_empty((B,) + shp + (C,)).permute(0, 4, 1, 2, 3) if channel_last[k]
+                   else gout.new_empty((B, C) + shp))
+    return out
+
+
+def _waverec3_bwd(ctx, gout):
+    g = torch.ops.waveformer.waverec3_level_backward(gout, list(ctx.ll_size), ctx.cl,
+                                                     ctx.wavelet)
+    return g[0], list(g[1:]), None
+
+
+waverec3_level.register_autograd(_waverec3_bwd, setup_context=_waverec3_setup)
 
 
 # ------------------------------------------------------------------------------------------
@@ -644,10 +753,13 @@ def _merge_bwd(ctx, gout):
 patch_merging.register_autograd(_merge_bwd, setup_context=_merge_setup)
 
 
-OPS = {"dwt3d": dwt3d, "idwt3d": idwt3d, "window_attn": window_attn, "msfuse": msfuse,
+OPS = {"dwt3d": dwt3d, "idwt3d": idwt3d, "wavedec3_level": wavedec3_level,
+       "waverec3_level": waverec3_level, "window_attn": window_attn, "msfuse": msfuse,
        "ccf_ffn": ccf_ffn, "patch_merging": patch_merging}
 # the backward kernels are ops too, so AOT autograd can trace a backward graph through them
 BACKWARD_OPS = {"dwt3d_backward": dwt3d_backward, "idwt3d_backward": idwt3d_backward,
+                "wavedec3_level_backward": wavedec3_level_backward,
+                "waverec3_level_backward": waverec3_level_backward,
                 "window_attn_backward": window_attn_backward, "msfuse_backward": msfuse_backward,
                 "ccf_ffn_backward": ccf_ffn_backward,
                 "patch_merging_backward": patch_merging_backward}

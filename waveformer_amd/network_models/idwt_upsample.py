@@ -6,7 +6,9 @@ at inference (ops.hf_refine; PyTorch modules under autograd).  The wavelet synth
 concatenation with the skip (:163) run as one wf_idwt3d_haar launch that writes straight into
 the first half of the concatenated buffer (with the skip in the same kernel,
 wf_idwt3d_haar_cl_cat); the surrounding convolutions run on the HIP conv3d_k3 kernel and the
-fused InstanceNorm + LeakyReLU passes (blocks.py).
+fused InstanceNorm + LeakyReLU passes (blocks.py).  Wavelets other than Haar (db2..db4) run
+one wf_idwt3d_level launch per level; under autograd both take their registered ops
+(waveformer::idwt3d, waveformer::waverec3_level) and torch.cat.
 """
 from __future__ import annotations
 
@@ -88,17 +90,18 @@ class UnetrIDWTBlock(nn.Module):
         wname = str(getattr(self.wavelet, "name", self.wavelet))
         if wname not in ("db1", "haar"):
             # longer filters (config 5): one wf_idwt3d_level launch per level, the finest
-            # written into the concatenation buffer; inference only
-            if torch.is_grad_enabled() and (inp.requires_grad or any(
-                    t.requires_grad for d in hf_coeffs for t in d.values())):
-                raise NotImplementedError(
-                    f"waveformer_amd: backward through wavelet {self.wavelet!r} not implemented")
+            # written into the concatenation buffer
             shp = hf_coeffs[-1]["aad"].shape
             size = tuple(2 * n - len(ops.WAVELETS[wname][0]) + 2 for n in shp[2:])
             B, C = inp.shape[:2]
             if skip.shape[0] != B or tuple(skip.shape[2:]) != size:
                 raise ValueError(f"skip {tuple(skip.shape)} does not match the IDWT output "
                                  f"{(B, C) + size}")
+            if torch.is_grad_enabled() and (inp.requires_grad or any(
+                    t.requires_grad for d in hf_coeffs for t in d.values())):
+                # training: a chain of waveformer::waverec3_level ops (HIP backward)
+                out = wfa.waverec3((inp,) + tuple(hf_coeffs), wname)
+                return self.conv_block(torch.cat((out, skip), dim=1))
             buf = torch.empty((B, C + skip.shape[1]) + size, dtype=inp.dtype, device=inp.device)
             ops.waverec3((inp,) + tuple(hf_coeffs), self.wavelet, out=buf[:, :C])
             buf[:, C:].copy_(skip)

@@ -323,7 +323,8 @@ class WaveletTransform3D(nn.Module):
     """ptwt.wavedec3 wrapper (wave_helper.py:343-353).  forward(x NCDHW, level) returns
     (LL, [dict_coarsest, ..., dict_finest]) like ptwt; Haar ('db1'/'haar', mode 'zero') runs on
     the wf_dwt3d_haar_fwd kernel.  The returned tensors have NCDHW shape and channel-last
-    strides (views of the kernel's band buffers)."""
+    strides (views of the kernel's band buffers).  db2..db4 run on the NCDHW kernels of
+    csrc/wavelet.hip (contiguous band views), differentiable like the Haar path."""
 
     def __init__(self, wavelet='db1', level=5, mode='zero'):
         super().__init__()
@@ -351,11 +352,12 @@ class WaveletTransform3D(nn.Module):
         if self.mode != "zero":
             raise NotImplementedError(f"waveformer_amd: wavelet mode {self.mode!r} not implemented")
         if str(getattr(self.wavelet, "name", self.wavelet)) not in ("db1", "haar"):
-            # longer filters (config 5: db2 3-level): NCDHW per-op kernels, inference only
-            if wfa.needs_grad(x):
-                raise NotImplementedError(
-                    f"waveformer_amd: backward through wavelet {self.wavelet!r} not implemented")
-            co = ops.wavedec3(x, self.wavelet, level)
+            # longer filters (config 5: db2 3-level): NCDHW per-op kernels; under autograd (or
+            # a compiler's trace) a chain of waveformer::wavedec3_level ops, the same kernel
+            if wfa.needs_grad(x) or torch.compiler.is_compiling():
+                co = wfa.wavedec3(x, self.wavelet, level)
+            else:
+                co = ops.wavedec3(x, self.wavelet, level)
             return co[0], co[1:]
         self._check()
         cur = x.permute(0, 2, 3, 4, 1).contiguous()

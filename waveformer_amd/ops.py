@@ -573,10 +573,22 @@ WAVELETS: Dict[str, Tuple[Tuple[float, ...], ...]] = {
 WAVELETS["haar"] = WAVELETS["db1"]
 
 
-def _filters(wavelet: str):
+def wavelet_name(wavelet) -> str:
+    """The name of a wavelet given as a string or a pywt.Wavelet-like object; raises for
+    anything but the implemented filter banks."""
     name = str(getattr(wavelet, "name", wavelet))
     if name not in WAVELETS:
         raise NotImplementedError(f"wavelet {name!r}: only {sorted(WAVELETS)} are implemented")
+    return name
+
+
+def wavelet_taps(wavelet) -> int:
+    """Filter length L of a wavelet (db1..db4: 2, 4, 6, 8)."""
+    return len(WAVELETS[wavelet_name(wavelet)][0])
+
+
+def _filters(wavelet: str):
+    name = wavelet_name(wavelet)
     return [(ctypes.c_float * len(f))(*f) for f in WAVELETS[name]], len(WAVELETS[name][0])
 
 
@@ -653,6 +665,64 @@ def waverec3(coeffs: Sequence, wavelet: str, out: Optional[torch.Tensor] = None)
                   o.stride(0), o.stride(1), _stream())
         x = o
     return x
+
+
+def dwt3d_bwd(gbands: torch.Tensor, size: Sequence[int], wavelet: str) -> torch.Tensor:
+    """The adjoint of dwt3d: gbands (8, B, C, d, h, w), the gradient of its output for an
+    input of spatial `size` (D, H, W) -> dx (B, C, D, H, W) (wf_dwt3d_bwd)."""
+    _check(gbands, "gbands", contiguous=False)
+    (lo, hi, _, _), L = _filters(wavelet)
+    D, H, W = (int(s) for s in size)
+    n = tuple((s + L - 1) // 2 for s in (D, H, W))
+    if gbands.dim() != 6 or gbands.shape[0] != 8 or tuple(gbands.shape[3:]) != n:
+        raise ValueError(f"dwt3d_bwd: expected band gradients (8, B, C) + {n} for an input of "
+                         f"{(D, H, W)}, got {tuple(gbands.shape)}")
+    gbands = gbands.contiguous()
+    B, C = gbands.shape[1:3]
+    dx = torch.empty((B, C, D, H, W), dtype=torch.float32, device=gbands.device)
+    _lib.call("wf_dwt3d_bwd", gbands.data_ptr(), dx.data_ptr(), B * C, D, H, W, lo, hi, L,
+              _stream())
+    return dx
+
+
+def idwt3d_level_bwd(gout: torch.Tensor, ll_size: Sequence[int], wavelet: str,
+                     channel_last: Sequence[bool] = (False,) * 8) -> List[torch.Tensor]:
+    """The adjoint of one waverec3 level: gout (B, C, Oz, Oy, Ox), the gradient of its output
+    -> [d LL, the 7 detail gradients (DETAIL_KEYS order)] (wf_idwt3d_level_bwd).  `ll_size` is
+    the spatial size of the level's LL input: per axis n = (O + L - 2) / 2 or n + 1; the extra
+    sample was cropped by the forward and gets gradient 0.  channel_last[k]: allocate gradient
+    k NCDHW-shaped with channel-last strides (the layout of the encoder's band views)."""
+    _check(gout, "gout", contiguous=False)
+    (_, _, rlo, rhi), L = _filters(wavelet)
+    if gout.dim() != 5:
+        raise ValueError(f"idwt3d_level_bwd: expected (B, C, Oz, Oy, Ox), got {tuple(gout.shape)}")
+    B, C = gout.shape[:2]
+    O = tuple(gout.shape[2:])
+    n = tuple((o + L - 2) // 2 for o in O)
+    if any(2 * m - L + 2 != o for m, o in zip(n, O)):
+        raise ValueError(f"idwt3d_level_bwd: {O} is not the output size of a {L}-tap level")
+    ll_size = tuple(int(s) for s in ll_size)
+    if len(ll_size) != 3 or any(s < m or s > m + 1 for s, m in zip(ll_size, n)):
+        raise ValueError(f"idwt3d_level_bwd: LL size {ll_size} does not fit details {n}")
+    if len(channel_last) != 8:
+        raise ValueError("idwt3d_level_bwd: channel_last needs one flag per band")
+    if not gout[0, 0].is_contiguous():
+        gout = gout.contiguous()
+    outs = []
+    for k in range(8):
+        shp = ll_size if k == 0 else n
+        if channel_last[k]:
+            t = torch.empty((B,) + shp + (C,), dtype=torch.float32,
+                            device=gout.device).permute(0, 4, 1, 2, 3)
+        else:
+            t = torch.empty((B, C) + shp, dtype=torch.float32, device=gout.device)
+        outs.append(t)
+    ptrs = (ctypes.c_void_p * 8)(*[t.data_ptr() for t in outs])
+    st = (ctypes.c_int64 * 40)(*[s for t in outs for s in t.stride()])
+    _lib.call("wf_idwt3d_level_bwd", gout.data_ptr(), gout.stride(0), gout.stride(1), B, C,
+              n[0], n[1], n[2], ll_size[0] - n[0], ll_size[1] - n[1], ll_size[2] - n[2], rlo, rhi,
+              L, ptrs, st, _stream())
+    return outs
 
 
 # ------------------------------------------------------------------------------------------
