@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define WF_ABI_VERSION 19
+#define WF_ABI_VERSION 20
 
 enum { WF_PREC_BF16 = 0, WF_PREC_BF16X3 = 1, WF_PREC_FP16 = 2 };
 
@@ -427,6 +427,25 @@ int wf_window_attention_fwd(const float* x, const float* ln_w, const float* ln_b
                             float* out, void* workspace, int64_t B, int64_t C, int64_t D1,
                             int64_t H1, int64_t W1, int64_t ws, int64_t heads, float scale,
                             int precision, void* stream);
+
+/* wf_window_attention_fwd_table (without norm1) over all nlev <= 4 LL levels of one Block at
+ * once: the levels share the weights, so they run as one qkv GEMM over sum(rows) logical rows
+ * (each row gathered from its own level), one core launch over sum(windows) and one proj GEMM,
+ * instead of three launches per level.  x[l]: channel-last (B, D_l, H_l, W_l, C) fp32, 16-byte
+ * aligned, allocations of their own or views; dhw: the nlev (D_l, H_l, W_l) triples, each
+ * tiling into 8^3 windows.  ws = 8, C = 16 * heads.  out: (sum_l B*D_l*H_l*W_l, C) fp32, level
+ * after level, each level window-major exactly as wf_window_attention_fwd_table writes it -- and
+ * bitwise what nlev such calls write.  Widths without a multi-level GEMM instantiation run as
+ * those nlev calls.  workspace: wf_window_attention_levels_workspace_bytes(...) bytes (the sum
+ * of the per-level sizes; < 0 for an invalid level list), 256-B aligned.                     */
+int64_t wf_window_attention_levels_workspace_bytes(const int64_t* dhw, int nlev, int64_t B,
+                                                   int64_t C, int precision);
+int wf_window_attention_fwd_levels(const float* const* x, const int64_t* dhw, int nlev,
+                                   const uint16_t* wqkv_bf16x2, const float* bqkv,
+                                   const float* table, const uint16_t* wproj_bf16x2,
+                                   const float* bproj, float* out, void* workspace, int64_t B,
+                                   int64_t C, int64_t heads, float scale, int precision,
+                                   void* stream);
 
 /* ---- a6: multi-scale fuse ------------------------------------------------------------- */
 /* Replaces the F.interpolate(trilinear, align_corners=False) + sum + shortcut of

@@ -90,6 +90,9 @@ SIGNATURES = {
     "wf_window_attention_workspace_bytes": (_I64, [_I64, _I64, _I64, _I64, _I64, _I]),
     "wf_window_attention_fwd": (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P,
                                      _I64, _I64, _I64, _I64, _I64, _I64, _I64, _F, _I, _P]),
+    "wf_window_attention_levels_workspace_bytes": (_I64, [_P, _I, _I64, _I64, _I]),
+    "wf_window_attention_fwd_levels": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I64, _I64,
+                                            _I64, _F, _I, _P]),
     "wf_msfuse_fwd": (_I, [_P, _P, _I, _P, _P, _P, _P, _F, _I64, _I64, _I64, _I64, _I64, _P]),
     "wf_ccf_ffn_workspace_bytes": (_I64, [_I64, _I64, _I64, _I64, _I64, _I64, _I]),
     "wf_ccf_ffn_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _F, _P, _P,
@@ -138,7 +141,7 @@ SIGNATURES = {
     "wf_transpose_cs": (_I, [_P, _P, _I64, _I64, _I64, _P]),
 }
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 _lock = threading.Lock()
 _lib = None
 _err = None

@@ -14,6 +14,7 @@
 //          carries Q, K, V and P as bf16 hi + lo pairs (3 MFMAs per product).
 //   proj : gemm_ares; rows stay in window-major order, which is exactly the reference's
 //          reshaped raster (Q1).
+#include "attn_levels.hpp"
 #include "kernels.hpp"
 
 namespace wf {
@@ -343,7 +344,13 @@ template <int P>
 __global__ __launch_bounds__(512, 2) void attn_tbl_kernel(const void* __restrict__ qkv,
                                                           const float* __restrict__ table,
                                                           void* __restrict__ out, int heads,
-                                                          int qsplit, float scale_log2) {
+                                                          int qsplit, float scale_log2,
+                                                          int64_t pair_end) {
+  // pair_end: windows [0, pair_end) may take the query-pair loop, the others take the
+  // one-sub-tile loop whatever the split.  The two loops differ in fp32 rounding when a tile
+  // after the first raises the running max: the pair loop rescales BOTH its sub-tiles when
+  // either asks for it.  A launch over several levels (wf_window_attention_fwd_levels) gives
+  // each level the loop its own launch would have taken, so its bits do not move.
   constexpr bool SPLIT = P == PREC_SPLIT;  // P: Prec (operand kind)
   constexpr int N = 512, HD = 16;
   constexpr int TBLN = 547;      // reachable rows of the (15^3, heads) table under Q2
@@ -435,7 +442,7 @@ __global__ __launch_bounds__(512, 2) void attn_tbl_kernel(const void* __restrict
   // by the split's 2^-16 residual).  Plain bf16 / fp16 keep the MFMA sums: their l must be
   // the sum of the same rounded P the numerator uses.
   constexpr bool VSUM = WF_ATTN_QP_VSUM && SPLIT;
-  if (nsub >= 16) {
+  if (nsub >= 16 && bw < pair_end) {
     // two independent 16-query sub-tiles per wave (st and st + 8): every K / V fragment read
     // from LDS feeds both, and the two sub-tiles' dependency chains (scores -> max -> exp ->
     // PV) interleave -- the single-sub-tile loop left the SIMDs waiting on those chains with
@@ -737,9 +744,11 @@ __global__ __launch_bounds__(512, 2) void attn_tbl_kernel(const void* __restrict
   }
 }
 
+bool attn_tbl_pair_loop(int64_t wh) { return wh >= 256; }
+
 int launch_attn_core(const void* qkv, const float* bias, void* out, float* lse, int64_t Bw,
                      int N, int heads, int hd, float scale, int prec, hipStream_t s,
-                     int table_ws) {
+                     int table_ws, int64_t pair_windows) {
   if (Bw <= 0) return WF_OK;
   const int64_t nblk = cdiv(N, kQB) * heads * Bw;
   if (nblk > 0x7fffffff) return fail(WF_E_SHAPE, "attention: too many (window, head) tiles");
@@ -755,11 +764,12 @@ int launch_attn_core(const void* qkv, const float* bias, void* out, float* lse, 
       // queries of one (window, head) split over 1, 2 or 4 workgroups: enough workgroups for
       // two per CU, each staging the window's K / V once
       const int64_t wh = Bw * heads;
-      const int qsplit = wh >= 512 ? 1 : (wh >= 256 ? 2 : 4);
+      const int qsplit = wh >= 512 ? 1 : (attn_tbl_pair_loop(wh) ? 2 : 4);
       const dim3 g1((unsigned)(wh * qsplit));
       auto k = split ? attn_tbl_kernel<PREC_SPLIT>
                      : (f16 ? attn_tbl_kernel<PREC_FP16> : attn_tbl_kernel<PREC_BF16>);
-      hipLaunchKernelGGL(k, g1, dim3(512), 0, s, qkv, bias, out, heads, qsplit, sl2);
+      const int64_t pair_end = pair_windows < 0 ? Bw : pair_windows;
+      hipLaunchKernelGGL(k, g1, dim3(512), 0, s, qkv, bias, out, heads, qsplit, sl2, pair_end);
       return check_launch("attention core (table bias, window per workgroup)");
     }
     // training (lse): the tiled kernel
@@ -946,4 +956,124 @@ extern "C" int wf_window_attention_fwd(const float* x, const float* ln_w, const 
   return wf_window_attention_fwd_train(x, ln_w, ln_b, ln_eps, wqkv_bf16x2, bqkv, bias,
                                        wproj_bf16x2, bproj, out, workspace, nullptr, B, C, D1,
                                        H1, W1, ws, heads, scale, precision, stream);
+}
+
+// ---- all LL levels of one Block in one launch set -----------------------------------------
+// The levels share the weights, the window and head_dim, and do not depend on one another, so
+// they are one problem of sum(rows) logical rows: the qkv GEMM gathers each row from its level
+// (MAP_LEVELS), the core runs over sum(windows), the proj GEMM is the identity-map one.  Every
+// row's arithmetic is what the per-level call does, so the outputs are bitwise equal: a GEMM row
+// does not depend on the rows it shares a launch with, and the core's result depends on its grid
+// only through which of its two loops a window takes, which the merged launch keeps per level.
+extern "C" int64_t wf_window_attention_levels_workspace_bytes(const int64_t* dhw, int nlev,
+                                                              int64_t B, int64_t C,
+                                                              int precision) {
+  AttnLevels L;
+  if (attn_levels_plan(dhw, nlev, B, C, C / 16, L)) return WF_E_SHAPE;
+  const int64_t rows = L.row0[nlev], e = act_bytes(precision);
+  return (((rows * 3 * C * e) + 255) & ~(int64_t)255) + (((rows * C * e) + 255) & ~(int64_t)255);
+}
+
+extern "C" int wf_window_attention_fwd_levels(const float* const* x, const int64_t* dhw, int nlev,
+                                              const uint16_t* wqkv_bf16x2, const float* bqkv,
+                                              const float* table, const uint16_t* wproj_bf16x2,
+                                              const float* bproj, float* out, void* workspace,
+                                              int64_t B, int64_t C, int64_t heads, float scale,
+                                              int precision, void* stream) {
+  AttnLevels L;
+  if (const char* why = attn_levels_plan(dhw, nlev, B, C, heads, L))
+    return fail(WF_E_SHAPE, std::string(__func__) + ": " + why);
+  WF_REQUIRE(valid_prec(precision), "unknown precision");
+  WF_REQUIRE_PTR(x);
+  for (int l = 0; l < nlev; ++l) {
+    WF_REQUIRE_PTR(x[l]);
+    WF_REQUIRE(reinterpret_cast<uintptr_t>(x[l]) % 16 == 0, "level sources must be 16-byte aligned");
+  }
+  WF_REQUIRE_PTR(wqkv_bf16x2);
+  WF_REQUIRE_PTR(table);
+  WF_REQUIRE_PTR(wproj_bf16x2);
+  WF_REQUIRE_PTR(out);
+  WF_REQUIRE_PTR(workspace);
+  constexpr int64_t ws = kAttnLevelsWs, N = ws * ws * ws;
+  const int64_t rows = L.row0[nlev];
+  const int64_t e = act_bytes(precision);
+  hipStream_t s = (hipStream_t)stream;
+  void* qkv = workspace;
+  void* ao = reinterpret_cast<char*>(workspace) + (((rows * 3 * C * e) + 255) & ~(int64_t)255);
+  const int obf = !store32(precision);
+  // 1. qkv = Linear(window_partition(x_l)) of every level
+  GemmArgs g{};
+  g.prec = precision;
+  g.a_src = x[0];
+  g.a_C = (int)C;
+  g.a_nseg = 1;
+  g.a_map = MAP_LEVELS;
+  g.mB = (int)B;
+  g.mws = (int)ws;
+  for (int l = 0; l < WF_MAX_LEVELS; ++l) {
+    const bool on = l < nlev;
+    g.lv_src[l] = on ? x[l] : x[0];
+    g.lv_row0[l] = on ? (int)L.row0[l] : 0x7fffffff;
+    g.lv_D[l] = on ? L.D[l] : (int)ws;
+    g.lv_H[l] = on ? L.H[l] : (int)ws;
+    g.lv_W[l] = on ? L.W[l] : (int)ws;
+  }
+  g.a_ln = LN_NONE;
+  g.w = wqkv_bf16x2;
+  g.M = rows;
+  g.N = (int)(3 * C);
+  g.K = (int)C;
+  g.epi = EPI_STORE;
+  g.bias = bqkv;
+  g.out = qkv;
+  g.out_bf16 = obf;
+  g.ldo = 3 * C;
+  // the core loop each level's own launch takes (attn_tbl_kernel, pair_end): the merged launch
+  // keeps it per level, so the levels on the query-pair loop must come first
+  int64_t pair_windows = 0;
+  bool prefix = true;
+  for (int l = 0; l < nlev; ++l) {
+    const int64_t wl = (L.row0[l + 1] - L.row0[l]) / N;
+    if (attn_tbl_pair_loop(wl * heads)) {
+      prefix = prefix && pair_windows == L.row0[l] / N;
+      pair_windows = L.row0[l + 1] / N;
+    }
+  }
+  if (!prefix || (!try_launch_gemm_rows(g, s, true) && !try_launch_gemm_kc(g, s))) {
+    // no multi-level instantiation takes this width (or a coarse level before a finer one):
+    // one call per level, into the same output
+    for (int l = 0; l < nlev; ++l) {
+      const int rc = window_attention_impl(x[l], nullptr, nullptr, 0.f, wqkv_bf16x2, bqkv, table,
+                                           (int)ws, wproj_bf16x2, bproj, out + L.row0[l] * C,
+                                           workspace, nullptr, B, C, L.D[l], L.H[l], L.W[l], ws,
+                                           heads, scale, precision, stream);
+      if (rc) return rc;
+    }
+    return WF_OK;
+  }
+  int rc = check_launch("wf_window_attention_fwd_levels(qkv)");
+  if (rc) return rc;
+  // 2. softmax(q k^T * scale + bias) v over all levels' windows
+  rc = launch_attn_core(qkv, table, ao, nullptr, rows / N, (int)N, (int)heads, 16, scale,
+                        precision, s, (int)ws, pair_windows);
+  if (rc) return rc;
+  // 3. proj; window-major rows, level after level
+  GemmArgs p{};
+  p.prec = precision;
+  p.a_src = ao;
+  p.a_bf16 = obf;
+  p.a_C = (int)C;
+  p.a_nseg = 1;
+  p.a_map = MAP_IDENTITY;
+  p.a_ln = LN_NONE;
+  p.w = wproj_bf16x2;
+  p.M = rows;
+  p.N = (int)C;
+  p.K = (int)C;
+  p.epi = EPI_STORE;
+  p.bias = bproj;
+  p.out = out;
+  p.out_bf16 = 0;
+  p.ldo = C;
+  return launch_gemm(p, s, "wf_window_attention_fwd_levels(proj)");
 }

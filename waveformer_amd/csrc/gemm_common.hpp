@@ -37,24 +37,29 @@ __device__ __forceinline__ void load8f(const void* src, int64_t off, float (&v)[
   }
 }
 
+// Raster row of window-major row m: token m % ws^3 of window m / ws^3 of a (B, D, H, W) raster
+// partitioned into ws^3 windows (window_partition, wave_helper.py:450-461).
+__device__ __forceinline__ int window_row_pos(int m, int ws, int mD, int mH, int mW) {
+  const int N = ws * ws * ws;
+  const int nWh = mH / ws, nWw = mW / ws, nW = (mD / ws) * nWh * nWw;
+  const int bw = m / N;
+  const int t = m - bw * N;
+  const int b = bw / nW;
+  int wi = bw - b * nW;
+  const int wx = wi % nWw;
+  wi /= nWw;
+  const int wy = wi % nWh, wz = wi / nWh;
+  const int tx = t % ws, ty = (t / ws) % ws, tz = t / (ws * ws);
+  return ((b * mD + wz * ws + tz) * mH + wy * ws + ty) * mW + wx * ws + tx;
+}
+
 // Source element offset of logical (row m, column k).
 template <int MAP>
 struct RowMapper {
   int pos;  // source raster row (MAP_MERGE: the (2z, 2y, 2x) corner)
   __device__ __forceinline__ RowMapper(const GemmArgs& g, int m) {
     if (MAP == MAP_WINDOW) {
-      const int ws = g.mws;
-      const int N = ws * ws * ws;
-      const int nWh = g.mH / ws, nWw = g.mW / ws, nW = (g.mD / ws) * nWh * nWw;
-      const int bw = m / N;
-      const int t = m - bw * N;
-      const int b = bw / nW;
-      int wi = bw - b * nW;
-      const int wx = wi % nWw;
-      wi /= nWw;
-      const int wy = wi % nWh, wz = wi / nWh;
-      const int tx = t % ws, ty = (t / ws) % ws, tz = t / (ws * ws);
-      pos = ((b * g.mD + wz * ws + tz) * g.mH + wy * ws + ty) * g.mW + wx * ws + tx;
+      pos = window_row_pos(m, g.mws, g.mD, g.mH, g.mW);
     } else if (MAP == MAP_MERGE) {
       const int d = g.mD >> 1, h = g.mH >> 1, w = g.mW >> 1;
       int r = m;
@@ -79,6 +84,29 @@ struct RowMapper {
     }
     return (int64_t)pos * g.K + k;
   }
+};
+
+// MAP_LEVELS: the level of row m, then MAP_WINDOW on that level's raster.  The offset is in
+// elements from g.a_src (= lv_src[0]), the level's own base pointer folded in.  The window is
+// 8 (the host checks g.mws: the table-bias attention core is its only caller), so the token
+// coordinates are shifts and three divisions by the level's window counts remain.  Plain
+// arithmetic on m -- no cross-lane read of the (wave-uniform) level -- so gemm_kc's loop hoists
+// it like MAP_WINDOW's.  The selects are spelled out: a dynamic index into the by-value argument
+// would put it in scratch.
+template <>
+struct RowMapper<MAP_LEVELS> {
+  int64_t base;  // lv_src[level] - a_src, then + pos * K
+  __device__ __forceinline__ RowMapper(const GemmArgs& g, int m) {
+    const int l = (m >= g.lv_row0[1]) + (m >= g.lv_row0[2]) + (m >= g.lv_row0[3]);
+    const int r0 = l == 0 ? g.lv_row0[0] : l == 1 ? g.lv_row0[1] : l == 2 ? g.lv_row0[2] : g.lv_row0[3];
+    const int mD = l == 0 ? g.lv_D[0] : l == 1 ? g.lv_D[1] : l == 2 ? g.lv_D[2] : g.lv_D[3];
+    const int mH = l == 0 ? g.lv_H[0] : l == 1 ? g.lv_H[1] : l == 2 ? g.lv_H[2] : g.lv_H[3];
+    const int mW = l == 0 ? g.lv_W[0] : l == 1 ? g.lv_W[1] : l == 2 ? g.lv_W[2] : g.lv_W[3];
+    const float* src = l == 0 ? g.lv_src[0] : l == 1 ? g.lv_src[1] : l == 2 ? g.lv_src[2] : g.lv_src[3];
+    const int pos = window_row_pos(m - r0, 8, mD, mH, mW);
+    base = (src - reinterpret_cast<const float*>(g.a_src)) + (int64_t)pos * g.K;
+  }
+  __device__ __forceinline__ int64_t offset(const GemmArgs&, int k) const { return base + k; }
 };
 
 // ---- LN_COMPUTE: the octets g4, g4 + 4, g4 + 8, ... of one row (the 4 lanes l15 + 16 g4 of a
@@ -214,6 +242,13 @@ __device__ __forceinline__ void store4(void* out, bool out_bf16, int64_t roff, i
 inline bool gemm_known_callsite(const GemmArgs& g) {
   return (g.a_map == MAP_WINDOW && g.epi == EPI_STORE) || (g.a_map == MAP_IDENTITY) ||
          (g.a_map == MAP_MERGE && g.epi == EPI_STORE);
+}
+// MAP_LEVELS is instantiated for the merged qkv GEMM of the window attention only: plain fp32
+// rows into a stored product (gemm_rows<9> serves K = 48 / N = 144, gemm_kc<3 | 6> K = 96 /
+// N = 288); the launchers return "not taken" for anything else
+inline bool gemm_levels_callsite(const GemmArgs& g) {
+  return g.a_map == MAP_LEVELS && g.epi == EPI_STORE && g.a_ln == LN_NONE && !g.a_bf16 &&
+         !g.a_gelu && !g.o_pstats && g.a_nseg == 1 && g.a_C == g.K && g.mws == 8;
 }
 // (prec, a_bf16) as compile-time tags: f(P, ABF16) is called with an
 // std::integral_constant<int, Prec> and an std::bool_constant.  bf16 activations only exist in

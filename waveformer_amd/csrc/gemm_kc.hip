@@ -350,9 +350,15 @@ static void go_kc(const GemmArgs& g, hipStream_t s) {
   typedef KcCfg<NT> C;
   const bool split = g.prec == PREC_SPLIT;
   void (*kern)(GemmArgs) = nullptr;
-  gemm_with_prec(g.prec, g.a_bf16 != 0, [&](auto P, auto ABF16) {
-    kern = gemm_kc_kernel<NT, P(), MAP, EPI, ABF16()>;
-  });
+  if constexpr (MAP == MAP_LEVELS) {  // fp32 rows only (gemm_levels_callsite)
+    kern = split ? gemm_kc_kernel<NT, PREC_SPLIT, MAP, EPI, false>
+                 : g.prec == PREC_FP16 ? gemm_kc_kernel<NT, PREC_FP16, MAP, EPI, false>
+                                       : gemm_kc_kernel<NT, PREC_BF16, MAP, EPI, false>;
+  } else {
+    gemm_with_prec(g.prec, g.a_bf16 != 0, [&](auto P, auto ABF16) {
+      kern = gemm_kc_kernel<NT, P(), MAP, EPI, ABF16()>;
+    });
+  }
   // 16-wave workgroups for every grid of >= 1024 8-wave workgroups: stage-1 merge
   // 209.8 -> 201.9 us, stage-3 pwconv 64.2 -> 61.4, config 5 45.6-45.8 -> 46.0 volumes/s
   // (profiles/r4_gemm/)
@@ -403,7 +409,7 @@ static void dispatch_kc(int nt, const GemmArgs& g, hipStream_t s) {
 // column tiles per workgroup gemm_kc would use for g (0: it does not take the shape)
 int gemm_kc_pick_nt(const GemmArgs& g) {
   if (g.N % 32 != 0 || g.K < 8 || g.M >= ((int64_t)1 << 31)) return 0;
-  if (!gemm_known_callsite(g)) return 0;
+  if (g.a_map == MAP_LEVELS ? !gemm_levels_callsite(g) : !gemm_known_callsite(g)) return 0;
   const int tiles = g.N / 16;
   static const int cand[] = {24, 12, 8, 6, 4, 3, 2, 1};
   // narrowest chunk the small-M search may go down to
@@ -412,7 +418,7 @@ int gemm_kc_pick_nt(const GemmArgs& g) {
   // redo it per column chunk: at N >= 384 (8+ chunks of 3 tiles) 6-tile chunks halve that work
   // (stage-4 qkv 52.3 -> 39.0 us, the 576-column qkv 16.1 -> 13.4 us; plain loaders measured
   // slower with fewer chunks, profiles/r6/r6ks2_ab.txt)
-  if ((g.a_gelu || g.a_map == MAP_WINDOW) && g.N >= 384) minnt = 6;
+  if ((g.a_gelu || g.a_map == MAP_WINDOW || g.a_map == MAP_LEVELS) && g.N >= 384) minnt = 6;
   // the split-K fc (kc_ksplit: GELU loader, K >= 1536, caller scratch): the widest chunk up to
   // 12 tiles -- 2 chunks of 192 at stage 4, 256 workgroups with the 4 k splits: 55.5 -> 48.0 us
   // per B = 8 launch against 6 tiles; at stage 3 (no split) one 12-tile chunk measured 71 -> 73.5
@@ -440,7 +446,11 @@ int gemm_kc_pick_nt(const GemmArgs& g) {
 int try_launch_gemm_kc(const GemmArgs& g, hipStream_t s) {
   const int nt = gemm_kc_pick_nt(g);
   if (nt == 0) return 0;
-  if (g.a_map == MAP_WINDOW) dispatch_kc<MAP_WINDOW, EPI_STORE>(nt, g, s);
+  if (g.a_map == MAP_LEVELS) {  // the chunk widths K = 96 / N = 288 picks (3 for small M, else 6)
+    if (nt == 6) go_kc<6, MAP_LEVELS, EPI_STORE>(g, s);
+    else if (nt == 3) go_kc<3, MAP_LEVELS, EPI_STORE>(g, s);
+    else return 0;
+  } else if (g.a_map == MAP_WINDOW) dispatch_kc<MAP_WINDOW, EPI_STORE>(nt, g, s);
   else if (g.a_map == MAP_MERGE) dispatch_kc<MAP_MERGE, EPI_STORE>(nt, g, s);
   else if (g.epi == EPI_LN_GELU) dispatch_kc<MAP_IDENTITY, EPI_LN_GELU>(nt, g, s);
   else if (g.epi == EPI_RESID) dispatch_kc<MAP_IDENTITY, EPI_RESID>(nt, g, s);

@@ -383,6 +383,10 @@ static void go_rows(const GemmArgs& g, dim3 grid, size_t lds, hipStream_t s) {
     // bf16 storage (PREC_BF16; bf16 activations only exist there)
     launch(g.a_bf16 ? gemm_rows_kernel<NT, PREC_BF16, MAP, EPI, true>
                     : gemm_rows_kernel<NT, PREC_BF16, MAP, EPI, false>);
+  } else if constexpr (MAP == MAP_LEVELS) {  // fp32 rows only (gemm_levels_callsite)
+    launch(g.prec == PREC_SPLIT  ? gemm_rows_kernel<NT, PREC_SPLIT, MAP, EPI, false>
+           : g.prec == PREC_FP16 ? gemm_rows_kernel<NT, PREC_FP16, MAP, EPI, false>
+                                 : gemm_rows_kernel<NT, PREC_BF16, MAP, EPI, false>);
   } else {
     gemm_with_prec(g.prec, g.a_bf16 != 0, [&](auto P, auto ABF16) {
       launch(gemm_rows_kernel<NT, P(), MAP, EPI, ABF16()>);
@@ -406,7 +410,7 @@ static void dispatch_nt(int nt, const GemmArgs& g, dim3 grid, size_t lds, hipStr
 
 int try_launch_gemm_rows(const GemmArgs& g, hipStream_t s, bool single_chunk_only) {
   if (g.N % 16 != 0 || g.K < 8 || g.M >= ((int64_t)1 << 31)) return 0;
-  if (!gemm_known_callsite(g)) return 0;
+  if (g.a_map == MAP_LEVELS ? !gemm_levels_callsite(g) : !gemm_known_callsite(g)) return 0;
   // the LN+GELU instantiations are specialised to the CCF_FFN pwconv's loader and storage
   const int64_t out_bytes = g.M * g.ldo * ((g.prec == PREC_BF16 || g.a_bf16) ? 2 : 4);
   if (g.epi == EPI_LN_GELU && (g.K > 64 || out_bytes >= ((int64_t)1 << 31) || (g.a_ln != LN_GIVEN && g.a_ln != LN_NONE) || g.a_gelu ||
@@ -438,6 +442,7 @@ int try_launch_gemm_rows(const GemmArgs& g, hipStream_t s, bool single_chunk_onl
   if (lds > 160 * 1024) return 0;
   const int chunks = tiles / nt;
   if (single_chunk_only && chunks > 1) return 0;
+  if (g.a_map == MAP_LEVELS && nt != 9) return 0;  // the one instantiation (K = 48 / N = 144)
   const int64_t ntiles = (g.M + 15) / 16;
   int64_t gx = cdiv(ntiles, 8);
   // ~2 workgroups of 8 waves per CU; one per CU when the weight chunk fills the LDS
@@ -445,7 +450,8 @@ int try_launch_gemm_rows(const GemmArgs& g, hipStream_t s, bool single_chunk_onl
   if (gx > cap) gx = cap;
   if (gx < 1) gx = 1;
   dim3 grid((unsigned)gx, (unsigned)chunks);
-  if (g.a_map == MAP_WINDOW) dispatch_nt<MAP_WINDOW, EPI_STORE>(nt, g, grid, lds, s);
+  if (g.a_map == MAP_LEVELS) go_rows<9, MAP_LEVELS, EPI_STORE>(g, grid, lds, s);
+  else if (g.a_map == MAP_WINDOW) dispatch_nt<MAP_WINDOW, EPI_STORE>(nt, g, grid, lds, s);
   else if (g.a_map == MAP_MERGE) dispatch_nt<MAP_MERGE, EPI_STORE>(nt, g, grid, lds, s);
   else if (g.epi == EPI_LN_GELU) dispatch_nt<MAP_IDENTITY, EPI_LN_GELU>(nt, g, grid, lds, s);
   else if (g.epi == EPI_RESID) dispatch_nt<MAP_IDENTITY, EPI_RESID>(nt, g, grid, lds, s);

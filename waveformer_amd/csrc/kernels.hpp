@@ -107,7 +107,12 @@ inline bool valid_prec(int p) { return p == PREC_BF16 || p == PREC_SPLIT || p ==
 // ---- A-resident MFMA GEMM:  out[m, n] = epilogue( sum_k A[m, k] * Wt[n, k] ) -------------
 // A rows are produced by a loader (gather + optional LayerNorm + bf16 rounding) into LDS once
 // per workgroup; the weight Wt [2][N][K] (bf16 hi plane, then lo plane) streams from L2.
-enum RowMap { MAP_IDENTITY = 0, MAP_WINDOW = 1, MAP_MERGE = 2 };
+// MAP_LEVELS: MAP_WINDOW over up to 4 rasters at once (the LL levels of one Block): logical row
+// m belongs to the level whose row range [lv_row0[l], lv_row0[l + 1]) holds it and is gathered
+// from lv_src[l] by MAP_WINDOW's arithmetic on (mB, lv_D[l], lv_H[l], lv_W[l], mws = 8).  Every
+// level's row count is a multiple of 8^3, so a 16-row tile never straddles two levels.
+enum RowMap { MAP_IDENTITY = 0, MAP_WINDOW = 1, MAP_MERGE = 2, MAP_LEVELS = 3 };
+constexpr int WF_MAX_LEVELS = 4;
 // LN_PARTIAL: a_stats holds a_np (mean, M2) pairs per row, each over K / a_np consecutive
 // columns (written by the producing kernel); the loader combines them (Chan et al.).
 enum LnMode { LN_NONE = 0, LN_GIVEN = 1, LN_COMPUTE = 2, LN_PARTIAL = 3 };
@@ -159,6 +164,10 @@ struct GemmArgs {
   int64_t kpart_bytes;   //   grids split the k loop over grid.z into (ksplit, M, N) fp32
                          //   partials, summed in split order by a second kernel + epilogue
   int ksplit;            // set by the launcher (kernel side), 1 = no split
+  // ---- MAP_LEVELS (fp32 sources, a_src = lv_src[0]; unused levels: lv_row0 = INT_MAX)
+  const float* lv_src[WF_MAX_LEVELS];
+  int lv_row0[WF_MAX_LEVELS];  // first logical row of the level
+  int lv_D[WF_MAX_LEVELS], lv_H[WF_MAX_LEVELS], lv_W[WF_MAX_LEVELS];
 };
 
 int launch_gemm(const GemmArgs& g, hipStream_t s, const char* who);
@@ -174,9 +183,13 @@ int try_launch_gemm_rows(const GemmArgs& g, hipStream_t s, bool single_chunk_onl
 // ---- windowed attention core over a (B_, N, 3C) qkv buffer (bf16, or fp32 when SPLIT) ----
 // table_ws != 0: `bias` is the (T, heads) relative_position_bias_table and the index is the
 // reference's formula for window table_ws (8 with head_dim 16 implemented)
+// pair_windows (table bias, inference): windows [0, pair_windows) may take the core's
+// query-pair loop, the rest its one-sub-tile loop (< 0: all may); attn_tbl_pair_loop(wh) is the
+// loop a launch of wh (window, head)s takes on its own
 int launch_attn_core(const void* qkv, const float* bias, void* out, float* lse, int64_t Bw,
                      int N, int heads, int hd, float scale, int prec, hipStream_t s,
-                     int table_ws = 0);
+                     int table_ws = 0, int64_t pair_windows = -1);
+bool attn_tbl_pair_loop(int64_t wh);
 
 // ---- depthwise 3^3 conv + bias + LayerNorm + GELU over a channel-last volume ------------
 // (bf16 storage for PREC_BF16, fp32 for PREC_SPLIT)

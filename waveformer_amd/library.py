@@ -10,6 +10,8 @@ them (attention.py:83-104, wave_helper.py:349 / :470-512, idwt_upsample.py:160).
   waveformer::wavedec3_level one level of ptwt.wavedec3 of an NCDHW volume, db1..db4, any sizes
   waveformer::waverec3_level one level of ptwt.waverec3, db1..db4 (strided coefficients)
   waveformer::window_attn    window_partition + Attention.forward + the Q1 reshape-reverse
+  waveformer::window_attn_levels  window_attn over all LL levels of a Block as one launch set
+                             (inference only; no autograd)
   waveformer::msfuse         the multi-scale trilinear fuse + shortcut (+ norm2 statistics)
   waveformer::ccf_ffn        norm2 + CCF_FFN + the Q4 double residual
   waveformer::patch_merging  PatchMerging(V2) (Q3 sub-lattices)
@@ -465,6 +467,26 @@ def _attn_bwd(ctx, gout, _gwork, _glse):
 window_attn.register_autograd(_attn_bwd, setup_context=_attn_setup)
 
 
+@torch.library.custom_op("waveformer::window_attn_levels", mutates_args=(), device_types="cuda")
+def window_attn_levels(xs: Sequence[Tensor], wqkv: Tensor, bqkv: Optional[Tensor], table: Tensor,
+                       wproj: Tensor, bproj: Optional[Tensor], heads: int, scale: float,
+                       prec: int) -> Tensor:
+    """window_attn (inference, table bias: ws 8, head_dim 16, the index buffer equal to the
+    reference's formula, no norm1) over the 2..4 LL levels xs of one multi-scale Block as one
+    launch set (wf_window_attention_fwd_levels).  Returns (sum of the levels' rows, C): the
+    levels' window-major outputs one after the other, each bitwise what window_attn gives for
+    that level alone.  No autograd: training keeps the per-level op."""
+    outs = ops.window_attention(xs[0], wqkv, bqkv, table.detach(), wproj, bproj, 8, heads, scale,
+                                None, prec=prec, more=tuple(xs[1:]))
+    return outs.buffer  # the one buffer the per-level views share
+
+
+@window_attn_levels.register_fake
+def _(xs, wqkv, bqkv, table, wproj, bproj, heads, scale, prec):
+    C = xs[0].shape[-1]
+    return xs[0].new_empty((sum(x.numel() // C for x in xs), C))
+
+
 # ------------------------------------------------------------------------------------------
 # a6: multi-scale fuse
 # ------------------------------------------------------------------------------------------
@@ -754,8 +776,9 @@ patch_merging.register_autograd(_merge_bwd, setup_context=_merge_setup)
 
 
 OPS = {"dwt3d": dwt3d, "idwt3d": idwt3d, "wavedec3_level": wavedec3_level,
-       "waverec3_level": waverec3_level, "window_attn": window_attn, "msfuse": msfuse,
-       "ccf_ffn": ccf_ffn, "patch_merging": patch_merging}
+       "waverec3_level": waverec3_level, "window_attn": window_attn,
+       "window_attn_levels": window_attn_levels, "msfuse": msfuse, "ccf_ffn": ccf_ffn,
+       "patch_merging": patch_merging}
 # the backward kernels are ops too, so AOT autograd can trace a backward graph through them
 BACKWARD_OPS = {"dwt3d_backward": dwt3d_backward, "idwt3d_backward": idwt3d_backward,
                 "wavedec3_level_backward": wavedec3_level_backward,

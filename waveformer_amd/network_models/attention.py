@@ -113,6 +113,25 @@ class Attention(nn.Module):
                                      float(self.scale), prec, train, self._formula_valid())
         return out
 
+    def forward_rasters(self, xs) -> list:
+        """forward_raster of each raster of xs, the LL levels of a multi-scale Block.  Two or
+        more levels run as one launch set (the waveformer::window_attn_levels op: one qkv
+        GEMM, one core launch, one proj GEMM for all of them, bitwise the per-level results)
+        where that op applies: the table-bias kernel's shape (ws 8, head_dim 16, the index
+        buffer equal to the formula), no gradient needed, not inside torch.compile.  Everything
+        else -- training included -- is one window_attn op per level."""
+        if (2 <= len(xs) <= 4 and self.window_size == 8 and self.head_dim == 16
+                and self._formula_valid() and not torch.compiler.is_compiling()
+                and not wfa.needs_grad(*xs, *self.parameters())):
+            self._check_train()
+            C = xs[0].shape[-1]
+            out = _OPS.window_attn_levels(list(xs), self.qkv.weight, self.qkv.bias,
+                                          self.relative_position_bias_table, self.proj.weight,
+                                          self.proj.bias, self.num_heads, float(self.scale),
+                                          ops.op_prec("attn"))
+            return [o.view(x.shape) for o, x in zip(out.split([x.numel() // C for x in xs]), xs)]
+        return [self.forward_raster(x) for x in xs]
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """x: (B_, N, C) token batches, N = window_size^3 (attention.py:83-104)."""
         B_, N, C = x.shape

@@ -479,7 +479,8 @@ class Block(nn.Module):
         the qkv loader); the interpolations, their sum, the shortcut and norm2's statistics
         are one msfuse kernel; norm2 + CCF_FFN + the double residual (Q4) are the FFN
         kernels' loader/epilogues.  Inference and training run the same torch.ops.waveformer
-        ops (their autograd is the HIP backward)."""
+        ops (their autograd is the HIP backward), except that inference attends all LL levels
+        in one launch set (Attention.forward_rasters; bitwise the per-level calls)."""
         x = self._prep(x)
         s_attn, s_mlp = self._branch_scales(x.shape[0], x.device)
         ln1 = (self.norm1.weight, self.norm1.bias, self.norm1.eps)
@@ -489,11 +490,11 @@ class Block(nn.Module):
             n = self.attn_computation_level
             if (self._hf_unused and x.is_cuda and not torch.is_grad_enabled()
                     and not torch.compiler.is_compiling()):
-                srcs = [self.attn.forward_raster(ll) for ll in self._ll_levels(x, ln1, n)]
+                srcs = self.attn.forward_rasters(self._ll_levels(x, ln1, n))
                 xh, stats = _OPS.msfuse(srcs, x, s_attn, float(self.norm2.eps), True)
                 return ffn_op(xh, stats, self.norm2, self.mlp, s_mlp), ()
             bands = self._levels(x, ln1, n)
-            srcs = [self.attn.forward_raster(b[0]) for b in bands]
+            srcs = self.attn.forward_rasters([b[0] for b in bands])
             hfs = [ops.bands_to_coeffs(b)[1] for b in bands]
         else:
             srcs = [self.attn.forward_raster(x, ln1)]

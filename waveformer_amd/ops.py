@@ -1412,14 +1412,23 @@ def window_attention(x_cl: torch.Tensor, wqkv: torch.Tensor, bqkv: Optional[torc
                      bias: torch.Tensor, wproj: torch.Tensor, bproj: Optional[torch.Tensor],
                      ws: int, heads: int, scale: float,
                      ln: Optional[Tuple[torch.Tensor, torch.Tensor, float]] = None,
-                     prec: Optional[int] = None) -> torch.Tensor:
+                     prec: Optional[int] = None, more: Sequence[torch.Tensor] = ()):
     """window_partition + Attention.forward + reshape-reverse (Q1) over a channel-last raster.
     Returns (B, D1, H1, W1, C) whose rows are the window-major attention outputs.  `bias` is
     the dense (heads, N, N) bias, or the ((2ws-1)^3, heads) table itself when the index is the
-    reference's formula (wf_window_attention_fwd_table, ws 8 / head_dim 16)."""
+    reference's formula (wf_window_attention_fwd_table, ws 8 / head_dim 16).
+
+    more: further rasters (B, D_l, H_l, W_l, C) attended with the same weights -- the coarser
+    LL levels of a multi-scale Block.  All levels then run as one launch set
+    (wf_window_attention_fwd_levels: table bias, no LayerNorm) and the result is a tuple of
+    per-level views, x_cl's first, of one output buffer; each is bitwise what a call on that
+    level alone returns."""
     _check(x_cl, "x")
     B, D1, H1, W1, C = x_cl.shape
     prec = _prec() if prec is None else prec
+    if more:
+        return _window_attention_levels((x_cl, *more), wqkv, bqkv, bias, wproj, bproj, ws, heads,
+                                        scale, ln, prec)
     wq = split_weight(wqkv, prec=prec)
     wp = split_weight(wproj, prec=prec)
     if bqkv is not None:
@@ -1446,6 +1455,42 @@ def window_attention(x_cl: torch.Tensor, wqkv: torch.Tensor, bqkv: Optional[torc
               out.data_ptr(), work.data_ptr(), B, C, D1, H1, W1, ws, heads, float(scale),
               prec, _stream())
     return out
+
+
+def _window_attention_levels(levels, wqkv, bqkv, bias, wproj, bproj, ws, heads, scale, ln, prec):
+    """window_attention(levels[0], ..., more=levels[1:])."""
+    B, C = levels[0].shape[0], levels[0].shape[4]
+    if ln is not None or ws != 8 or tuple(bias.shape) != ((2 * ws - 1) ** 3, heads):
+        raise ValueError("window_attention(more=...): the table bias (ws 8, head_dim 16) without "
+                         "a LayerNorm only")
+    dhw: List[int] = []
+    for x in levels:
+        _check(x, "x")
+        if x.dim() != 5 or x.shape[0] != B or x.shape[4] != C:
+            raise ValueError("window_attention(more=...): level batch/channels mismatch")
+        dhw.extend(x.shape[1:4])
+    for t, name in ((bqkv, "qkv.bias"), (bproj, "proj.bias"), (bias, "bias")):
+        if t is not None:
+            _check(t, name)
+    wq = split_weight(wqkv, prec=prec)
+    wp = split_weight(wproj, prec=prec)
+    darr = (ctypes.c_int64 * len(dhw))(*dhw)
+    wsb = _lib.query("wf_window_attention_levels_workspace_bytes", darr, len(levels), B, C, prec)
+    rows = [x.numel() // C for x in levels]
+    out = torch.empty((sum(rows), C), dtype=torch.float32, device=levels[0].device)
+    work = torch.empty(max(wsb, 0), dtype=torch.uint8, device=out.device)
+    arr = (ctypes.c_void_p * len(levels))(*[x.data_ptr() for x in levels])
+    _lib.call("wf_window_attention_fwd_levels", arr, darr, len(levels), wq.data_ptr(),
+              _ptr(bqkv), bias.data_ptr(), wp.data_ptr(), _ptr(bproj), out.data_ptr(),
+              work.data_ptr(), B, C, heads, float(scale), prec, _stream())
+    views = LevelViews(o.view(x.shape) for o, x in zip(out.split(rows), levels))
+    views.buffer = out
+    return views
+
+
+class LevelViews(tuple):
+    """window_attention(more=...)'s result: the per-level views, and as `.buffer` the one
+    (sum of rows, C) tensor they are views of."""
 
 
 # ------------------------------------------------------------------------------------------
