@@ -170,21 +170,29 @@ def test_conv3d_k3_fused_instnorm_stats(B, Cin, Cout, S):
     assert C.rel_l2(st[:, 1], rstd) <= 1e-5
 
 
-@pytest.mark.parametrize("src,s", [((4, 5, 6), 4), ((8, 7, 3), 2)])
+@pytest.mark.parametrize("src,s", [((4, 5, 6), 4), ((8, 7, 3), 2), ((2, 3, 2), 8), ((2, 2, 3), 6)])
 def test_upsample_cl_autograd_adjoint(src, s):
     """Training path of ProjectionUpsample's nn.Upsample(align_corners=True): the HIP adjoint
-    (three separable gather passes) vs PyTorch's autograd of F.interpolate on the CPU."""
+    (three separable gather passes) vs PyTorch's autograd of F.interpolate on the CPU.  x8 and
+    x6 of 2 or 3 samples: ratios (Lout - 1) / (Lin - 1) of 8.5 .. 15, far past the model's own
+    (test_gpu_train_kernels.py::test_interp_adjoint_axis_ac).
+
+    The gradient's reference is fp64 autograd: the framework's fp32 backward (one scatter-add of
+    up to 512 terms per input) is itself 1.17e-6 from fp64 at ((2, 3, 2), 8) and 6.6e-7 at
+    ((2, 2, 3), 6) (4.8e-7 / 2.4e-7 at the x4 / x2 cases), as large as the bar; the separable
+    fp32 form the kernel evaluates is 1.3e-7 .. 2.9e-7 from fp64."""
     from waveformer_amd import autograd as wfa
     x = seeded_randn((2, 8) + src, 17)
     size = tuple(v * s for v in src)
     g = seeded_randn((2, 8) + size, 18)
-    xc = x.clone().requires_grad_(True)
-    F.interpolate(xc, size=size, mode="trilinear", align_corners=True).backward(g)
+    xc = x.double().requires_grad_(True)
+    F.interpolate(xc, size=size, mode="trilinear", align_corners=True).backward(g.double())
     xg = x.cuda().requires_grad_(True)
     y = wfa.upsample_cl(xg, size)
     want_y = F.interpolate(x, size=size, mode="trilinear", align_corners=True)
     assert C.rel_l2(y, want_y) <= 1e-6
     y.backward(g.cuda())
+    print(f"upsample_cl {src} x{s}: y {C.rel_l2(y, want_y):.3e} dx {C.rel_l2(xg.grad, xc.grad):.3e}")
     assert C.rel_l2(xg.grad, xc.grad) <= 1e-6
 
 

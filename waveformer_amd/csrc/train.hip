@@ -626,8 +626,13 @@ __global__ __launch_bounds__(256) void interp_adjoint_kernel(
     int64_t t = idx / inner;
     const int i = (int)(t % Lin);
     const int64_t o = t / Lin;
-    int pmin = (int)floorf(((float)i - 0.5f) * r - 0.5f) - 2;
-    int pmax = (int)ceilf(((float)i + 1.5f) * r - 0.5f) + 2;
+    // the outputs p whose source index lies in (i - 1, i + 1), with a margin for the float
+    // rounding of the bounds (the weight test below makes the sum exact):
+    // align_corners=False: src = (p + 0.5) / r - 0.5;  True: src = p / r (Lin = 1: every p)
+    int pmin = AC ? (int)floorf(((float)i - 1.f) * r) - 1
+                  : (int)floorf(((float)i - 0.5f) * r - 0.5f) - 2;
+    int pmax = AC ? (int)ceilf(((float)i + 1.f) * r) + 1
+                  : (int)ceilf(((float)i + 1.5f) * r - 0.5f) + 2;
     pmin = pmin < 0 ? 0 : pmin;
     pmax = pmax > Lout - 1 ? Lout - 1 : pmax;
     const float* src = in + o * Lout * inner + e;
