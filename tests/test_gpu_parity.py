@@ -334,8 +334,12 @@ def test_patch_embed(cin, S):
 @pytest.mark.parametrize("ws,heads,dim,B_", [(8, 3, 48, 2), (8, 24, 384, 1), (2, 1, 48, 5),
                                              (2, 1, 384, 2), (4, 2, 64, 3), (8, 1, 96, 1),
                                              (8, 1, 192, 1), (12, 3, 48, 1), (4, 1, 128, 2),
-                                             (4, 2, 64, 1)])
+                                             (4, 2, 64, 1), (8, 3, 48, 96), (8, 3, 48, 176)])
 def test_attention_vs_oracle(ws, heads, dim, B_):
+    """The ws 8 / head_dim 16 cases run attn_tbl_kernel; windows x heads picks its form
+    (launch_attn_core): 6 and 24 split the queries over 4 workgroups and walk one 16-query
+    sub-tile at a time, 288 (>= 256) splits over 2 and walks two at a time, once per wave, 528
+    (>= 512) does not split and walks two at a time, twice per wave."""
     import waveformer_amd.network_models as NM
     from oracle.weight_rule import rule_state_dict
     m = NM.Attention(dim, num_heads=heads, qkv_bias=True, window_size=ws)

@@ -56,23 +56,17 @@ __device__ __forceinline__ void load8_split(const void* base, int64_t off, bf16x
   }
 }
 
-// WS == 0: `bias` is the dense (heads, N, N) relative-position bias.  WS == 8 (ws % 4 == 0
-// in general): `bias` is the (T, heads) relative_position_bias_table itself; its column h is
-// staged in LDS (pre-scaled by log2 e) and each score's row is the reference's index formula
-// (attention.py:40-56, with the Q2 depth stride 3 ws - 1) evaluated from the query / key
-// coordinates -- the (heads, N, N) tensor (805 MB of L2 reads per stage-1 launch) is never
-// touched.  The 4 keys a lane holds share (z, y) and have consecutive x, so their indices are
-// i0, i0 - 1, i0 - 2, i0 - 3.
-template <int HD, int KT, int P, int WS = 0>
+// The tiled core for any window and head_dim; `bias` is the dense (heads, N, N)
+// relative-position bias.  It also serves training: with `lse` it writes the row log-sum-exp
+// the backward recomputes P from.  (The table-bias form of the default window is
+// attn_tbl_kernel, inference only.)
+template <int HD, int KT, int P>
 __global__ __launch_bounds__(256) void attn_core_kernel(const void* __restrict__ qkv,
                                                         const float* __restrict__ bias,
                                                         void* __restrict__ out,
                                                         float* __restrict__ lse, int N,
                                                         int heads, float scale_log2) {
   constexpr bool SPLIT = P == PREC_SPLIT;  // P: Prec (operand kind)
-  constexpr int TBLN = WS ? (2 * WS - 2) * (3 * WS - 1) + (2 * WS - 2) * (2 * WS - 1) + 2 * WS - 1
-                          : 1;  // reachable table rows (Q2 collapses the (2ws-1)^3 table)
-  __shared__ float tb[TBLN];
   constexpr int NC = HD / 16;  // 16-wide head_dim chunks
   constexpr int NKT = KT / 16; // 16-key sub-tiles per tile
   constexpr int KS = HD + 4, VS = KT + 4;
@@ -115,14 +109,7 @@ __global__ __launch_bounds__(256) void attn_core_kernel(const void* __restrict__
 #pragma unroll
   for (int c = 0; c < NC; ++c) o[c] = f32x4{0, 0, 0, 0};
   float mrun = -INFINITY, lrun = 0.f;
-  const float* brow = bias + ((int64_t)h * N + (qv ? q : 0)) * (WS ? 0 : N);
-  int qbase = 0;
-  if (WS) {
-    for (int i = tid; i < TBLN; i += 256) tb[i] = bias[(int64_t)i * heads + h] * 1.4426950408889634f;
-    const int qq = qv ? q : 0;
-    const int qz = qq / (WS * WS), qy = (qq / WS) % WS, qx = qq % WS;
-    qbase = (qz + WS - 1) * (3 * WS - 1) + (qy + WS - 1) * (2 * WS - 1) + (qx + WS - 1);
-  }
+  const float* brow = bias + ((int64_t)h * N + (qv ? q : 0)) * N;
 
   for (int k0 = 0; k0 < N; k0 += KT) {
     __syncthreads();
@@ -169,11 +156,7 @@ __global__ __launch_bounds__(256) void attn_core_kernel(const void* __restrict__
     for (int kt = 0; kt < NKT; ++kt) {
       const int kb = k0 + kt * 16 + g4;
       f32x4 bv;
-      if (WS) {  // already scaled by log2 e
-        const int kz = kb / (WS * WS), ky = (kb / WS) % WS, kx = kb % WS;
-        const int i0 = min(max(qbase - (kz * (3 * WS - 1) + ky * (2 * WS - 1) + kx), 3), TBLN - 1);
-        bv = f32x4{tb[i0], tb[i0 - 1], tb[i0 - 2], tb[i0 - 3]};
-      } else if (kb + 3 < N) {
+      if (kb + 3 < N) {
         bv = *reinterpret_cast<const f32x4*>(brow + kb) * 1.4426950408889634f;
       } else {
         bv.x = kb + 0 < N ? brow[kb + 0] : 0.f;
@@ -260,8 +243,9 @@ __global__ __launch_bounds__(256) void attn_core_kernel(const void* __restrict__
 //   O^T = V^T P^T : 32 keys per MFMA, the B operand is the lane's two 4-key score quads of two
 //                 16-key sub-tiles as they come out of the S MFMAs (the K-slot order is matched
 //                 by reading V at the same keys), x3 for the split;
-//   l   = 1^T P^T : the softmax row sums on the same B operands (a ones A operand, hi + lo),
-//                 instead of an add per score on the VALU; every accumulator row holds the sum.
+//   l   = 1^T P^T : bf16 / fp16 operands: the softmax row sums on the same B operands (a ones A
+//                 operand), instead of an add per score on the VALU; every accumulator row
+//                 holds the sum.  Split operands add the fp32 exponentials (attn_tbl_tiles).
 // The bias index is the reference's formula (attention.py:40-56, Q2 depth stride 3 ws - 1)
 // with the key part reduced to per-tile constants: a 64-key tile is one z slice of the window.
 // The table is staged REVERSED, so a lane's 16 bias values of a tile are 4 ascending runs of 4
@@ -294,91 +278,202 @@ __device__ __forceinline__ int kswz(int row) {  // 16-B chunk XOR of a K row (se
   return (0x78 >> (2 * ((row >> 2) & 3))) & 3;  // {0, 2, 3, 1}[(row >> 2) & 3]
 }
 
-// WF_ATTN_MFMA_SUM=0: the softmax row sums as fp32 VALU adds instead of the ones-operand
-// MFMAs (4 of the 18 MFMAs per 64-key tile); measured slower -- 191 vs 171 us per B = 8
-// stage-1 launch (profiles/r4_attention_rowsum_ab.txt): the kernel's VALU, not its MFMA
-// pipe, is the tighter resource.  This holds for the one-sub-tile loop and the bf16 / fp16
-// operands; the default query-pair loop with split operands sums on the VALU (WF_ATTN_QP_VSUM).
-#ifndef WF_ATTN_MFMA_SUM
-#define WF_ATTN_MFMA_SUM 1
-#endif
-// WF_ATTN_BPERMUTE: the per-tile max exchange across the 4 key groups of a query column as
-// __shfl_xor (ds_bpermute, LDS crossbar; default) or as v_permlane16/32_swap (VALU, 0).  The
-// round-5 kernel-trace A/B (profiles/r5_attention_ab.txt) has the bpermute form 162.8 vs
-// 169.1 us per B = 8 stage-1 launch: the kernel's VALU is its tighter resource, and the swap
-// form adds VALU work.  A software-pipelined variant (tile t + 1's score MFMAs issued before
-// tile t's softmax) measured 174.8 us and was dropped.
-#ifndef WF_ATTN_BPERMUTE
-#define WF_ATTN_BPERMUTE 1
-#endif
-#ifndef WF_ATTN_T4  // 1: bias quads as single ds_read_b128 (A/B; 0: four scalar reads)
-#define WF_ATTN_T4 1
-#endif
-// WF_ATTN_LAZY (round 6): the running max is kept while no score of a 64-key tile exceeds it
-// by more than 2^WF_ATTN_TAU in the exp2 domain (a lane-local max + one wave ballot); only then
-// does the tile pay the cross-group max exchange (two ds_bpermute round trips on the
-// critical path), the alpha exponential and the o / l rescale.  The exponentials of a kept tile
-// are at most 2^TAU; the normalisation o / l is the same quotient, so this changes only fp32
-// rounding.  0: the max is exchanged and the rescale applied on every tile (round 5).
-#ifndef WF_ATTN_LAZY
-#define WF_ATTN_LAZY 1
-#endif
-#ifndef WF_ATTN_TAU
-#define WF_ATTN_TAU 16.0f
-#endif
-// WF_ATTN_DOT2 (round 6, bf16x3): the split's lo part of a pair of probabilities is
-// bf16(p - hi) with p - hi from one v_dot2c_f32_bf16 per value (the packed hi pair against
-// (-1, 0) / (0, -1), accumulated onto p) instead of unpacking hi back to fp32 and subtracting
-// (two VALU ops per value).  p - hi is exact in fp32, so the operands are bitwise the same.
-#ifndef WF_ATTN_DOT2
-#define WF_ATTN_DOT2 1
-#endif
-// WF_ATTN_QP (round 6): two 16-query sub-tiles per wave in one loop (see the kernel); 0: one
-#ifndef WF_ATTN_QP_VSUM
-#define WF_ATTN_QP_VSUM 1
-#endif
-#ifndef WF_ATTN_QP
-#define WF_ATTN_QP 1
-#endif
+namespace tbl {
+constexpr int N = 512, HD = 16;
+constexpr int TBLN = 547;  // reachable rows of the (15^3, heads) table under Q2
+constexpr int KS = 32;     // K row: hi[16] | lo[16], chunks swizzled (kswz)
+// V: [hi, lo][key/4][hd][4 keys], each key-quad block padded to 136 B so the staging
+// stores (lanes 64 / 128 B apart) spread over the banks; the loop's 16-lane reads stay
+// contiguous inside one block
+constexpr int VB = HD * 4 + 4;
+constexpr int VQ = (N / 4) * VB;
+// the reversed table as overlapping quads: tq[i] = {tbr[i], tbr[i+1], tbr[i+2], tbr[i+3]},
+// so a lane's 4 consecutive bias values are one aligned ds_read_b128
+constexpr int TQ_BYTES = TBLN * 16;
+// Lazy rescale: the running max is kept while no score of a 64-key tile exceeds it by more
+// than 2^kTau in the exp2 domain (a lane-local max + one wave ballot); only then does the tile
+// pay the cross-group max exchange (two ds_bpermute round trips on the critical path), the
+// alpha exponential and the o / l rescale.  The exponentials of a kept tile are at most
+// 2^kTau; the normalisation o / l is the same quotient, so this changes only fp32 rounding.
+constexpr float kTau = 16.0f;
+}  // namespace tbl
+
+// The tile loop of attn_tbl_kernel over this wave's 16-query sub-tiles, NQ at a time (sub-tiles
+// st, st + 8, ...; q0 = the workgroup's first query).  NQ = 2: every K / V fragment read from
+// LDS feeds both sub-tiles, and their dependency chains (scores -> max -> exp -> PV)
+// interleave -- with one sub-tile the SIMDs wait on those chains with four waves each (LDS
+// caps the workgroups at two per CU).  The two forms differ in fp32 rounding when a tile after
+// the first raises the running max: NQ = 2 rescales BOTH its sub-tiles when either asks for it.
+// What the loop does, each against alternatives that were built and measured (they and their
+// measurements are in the history before this commit and in DESIGN 6):
+//  * the max exchange across the 4 key groups of a query column is __shfl_xor (ds_bpermute, LDS
+//    crossbar), not v_permlane16/32_swap: the kernel's VALU is its tighter resource
+//    (profiles/r5_attention_ab.txt);
+//  * bf16 / fp16 operands take the softmax row sums as ones-operand MFMAs (4 of the 18 per
+//    64-key tile), not VALU adds (profiles/r4_attention_rowsum_ab.txt): their l must be the sum
+//    of the same rounded P the numerator uses;
+//  * split operands sum the fp32 exponentials on the VALU (each lane's partial over its 4 keys
+//    per 16-key block, the 4 lanes of a query reduced once at the end): 157.0 vs 159.6 us per
+//    B = 8 stage-1 launch, interleaved (profiles/r6/r6n_attn_vsum_ab.txt), and closer to exact
+//    by the split's 2^-16 residual.  The order is the same for NQ = 1 and 2: a volume's result
+//    must not depend on the batch (the qsplit = 4 launches of small grids run NQ = 1);
+//  * the split's lo part of a pair of probabilities comes from split_pair (v_dot2c_f32_bf16
+//    against the packed hi pair), bitwise the unpack-and-subtract form.
+template <int P, int NQ>
+__device__ __forceinline__ void attn_tbl_tiles(const void* __restrict__ qkv, void* __restrict__ out,
+                                               const f32x4* tq, const uint16_t* Ks,
+                                               const uint16_t* Vq, int64_t row0, int q0, int h,
+                                               int heads, int nsub, float scale_log2) {
+  using namespace tbl;
+  constexpr bool SPLIT = P == PREC_SPLIT;
+  constexpr bool VSUM = SPLIT;  // row sums on the VALU (see above)
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int l15 = lane & 15, g4 = lane >> 4;
+  const int C = heads * HD, ld = 3 * C;
+  const int kch = 8 * (g4 ^ kswz(l15));  // this lane's K chunk (rows t*64 + kt*16 + l15)
+  const bf16x8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
+  const short one = (short)op_cvt<P>(1.0f);
+  const bf16x8 ones = bf16x8{one, one, one, one, one, one, one, one};
+  for (int st = wid; st < nsub; st += 8 * NQ) {
+    int qq[NQ], rbq[NQ];
+    bf16x8 b1[NQ], b2[NQ];
+    f32x4 o[NQ], l4[NQ];
+    float mrun[NQ];
+#pragma unroll
+    for (int u = 0; u < NQ; ++u) {
+      const int q = q0 + (st + 8 * u) * 16 + l15;
+      qq[u] = q;
+      // B operands of S: slots 8 g4 .. +7 <- Q'[q][8 (g4 & 1) ..]: [Q'h | Q'h] and [Q'l | 0]
+      bf16x8 hi = z8, lo = z8;
+      load8_split_scaled<P>(qkv, (row0 + q) * ld + h * HD + 8 * (g4 & 1), scale_log2, hi, lo);
+      b1[u] = hi;
+      b2[u] = (SPLIT && g4 < 2) ? lo : z8;
+      const int qz = q >> 6, qy = (q >> 3) & 7, qx = q & 7;
+      // reversed-table base of tile 0: (TBLN - 1) - index(q, key (0, 2 (g4 >> 1), 4 (g4 & 1)))
+      rbq[u] = (TBLN - 1) - ((qz + 7) * 23 + (qy + 7) * 15 + (qx + 7)) +
+               ((g4 >> 1) * 15 + 4 * (g4 & 1));
+      o[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+      l4[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+      mrun[u] = -INFINITY;
+    }
+#pragma clang loop unroll_count(NQ == 1 ? 2 : 1)
+    for (int t = 0; t < 8; ++t) {  // 64-key tiles (one z slice of the window each)
+      // S^T of tile t: 4 sub-tiles of 16 keys, the accumulator starting at the bias
+      f32x4 s[NQ][4];
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt) {
+        const bf16x8 a = *reinterpret_cast<const bf16x8*>(&Ks[(t * 64 + kt * 16 + l15) * KS + kch]);
+#pragma unroll
+        for (int u = 0; u < NQ; ++u) {
+          s[u][kt] = mma32<P>(a, b1[u], tq[rbq[u] + 23 * t + 30 * kt]);
+          if (SPLIT) s[u][kt] = mma32<P>(a, b2[u], s[u][kt]);
+        }
+      }
+      float lmax[NQ];
+      bool big = false;
+#pragma unroll
+      for (int u = 0; u < NQ; ++u) {
+        lmax[u] = s[u][0][0];  // a chain, so the compiler pairs it into v_max3_f32
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+          for (int i = (kt == 0 ? 1 : 0); i < 4; ++i) lmax[u] = fmaxf(lmax[u], s[u][kt][i]);
+        big = big || lmax[u] > mrun[u] + kTau;
+      }
+      if (__builtin_amdgcn_ballot_w64(big) != 0) {  // wave-uniform
+#pragma unroll
+        for (int u = 0; u < NQ; ++u) {
+          float tmax = fmaxf(mrun[u], lmax[u]);
+          tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
+          tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+          const float alpha = __builtin_amdgcn_exp2f(mrun[u] - tmax);  // 0 on the first tile
+          mrun[u] = tmax;
+          o[u] *= alpha;
+          l4[u] *= alpha;
+        }
+      }
+      // P^T operand words: pairs of 16-bit values, hi and (bf16x3) lo parts
+      uint32_t ph[NQ][4][2], pl[NQ][4][2];
+#pragma unroll
+      for (int u = 0; u < NQ; ++u)
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+          for (int i = 0; i < 4; i += 2) {
+            const float e0 = __builtin_amdgcn_exp2f(s[u][kt][i] - mrun[u]);
+            const float e1 = __builtin_amdgcn_exp2f(s[u][kt][i + 1] - mrun[u]);
+            if (VSUM) l4[u][0] += e0 + e1;
+            split_pair<P>(e0, e1, ph[u][kt][i >> 1], pl[u][kt][i >> 1]);
+          }
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int o1 = (16 * t + 8 * j + g4) * VB + l15 * 4;
+        const int o2 = (16 * t + 8 * j + 4 + g4) * VB + l15 * 4;
+        const bf16x4 v1 = *reinterpret_cast<const bf16x4*>(&Vq[o1]);
+        const bf16x4 v2 = *reinterpret_cast<const bf16x4*>(&Vq[o2]);
+        const bf16x8 vh = bf16x8{v1[0], v1[1], v1[2], v1[3], v2[0], v2[1], v2[2], v2[3]};
+        bf16x8 vl = z8;
+        if (SPLIT) {
+          const bf16x4 w1 = *reinterpret_cast<const bf16x4*>(&Vq[VQ + o1]);
+          const bf16x4 w2 = *reinterpret_cast<const bf16x4*>(&Vq[VQ + o2]);
+          vl = bf16x8{w1[0], w1[1], w1[2], w1[3], w2[0], w2[1], w2[2], w2[3]};
+        }
+#pragma unroll
+        for (int u = 0; u < NQ; ++u) {
+          const bf16x8 pb = __builtin_bit_cast(
+              bf16x8, u32x4{ph[u][2 * j][0], ph[u][2 * j][1], ph[u][2 * j + 1][0], ph[u][2 * j + 1][1]});
+          if (SPLIT) {
+            const bf16x8 plb = __builtin_bit_cast(
+                bf16x8, u32x4{pl[u][2 * j][0], pl[u][2 * j][1], pl[u][2 * j + 1][0], pl[u][2 * j + 1][1]});
+            o[u] = mma32<P>(vl, pb, o[u]);
+            o[u] = mma32<P>(vh, plb, o[u]);
+            if (!VSUM) l4[u] = mma32<P>(ones, plb, l4[u]);
+          }
+          o[u] = mma32<P>(vh, pb, o[u]);
+          if (!VSUM) l4[u] = mma32<P>(ones, pb, l4[u]);
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < NQ; ++u) {
+      if (VSUM) {  // the 4 lanes (g4) of query l15
+        l4[u][0] += __shfl_xor(l4[u][0], 16, 64);
+        l4[u][0] += __shfl_xor(l4[u][0], 32, 64);
+      }
+      const float inv = 1.f / l4[u][0];
+      const int64_t off = (row0 + qq[u]) * C + h * HD + 4 * g4;
+      if (store32(P)) {
+        *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(out) + off) = o[u] * inv;
+      } else {
+        bf16x4 r;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) r[i] = (short)f2bf(o[u][i] * inv);
+        *reinterpret_cast<bf16x4*>(reinterpret_cast<uint16_t*>(out) + off) = r;
+      }
+    }
+  }
+}
+
 template <int P>
 __global__ __launch_bounds__(512, 2) void attn_tbl_kernel(const void* __restrict__ qkv,
                                                           const float* __restrict__ table,
                                                           void* __restrict__ out, int heads,
                                                           int qsplit, float scale_log2,
                                                           int64_t pair_end) {
-  // pair_end: windows [0, pair_end) may take the query-pair loop, the others take the
-  // one-sub-tile loop whatever the split.  The two loops differ in fp32 rounding when a tile
-  // after the first raises the running max: the pair loop rescales BOTH its sub-tiles when
-  // either asks for it.  A launch over several levels (wf_window_attention_fwd_levels) gives
-  // each level the loop its own launch would have taken, so its bits do not move.
+  // pair_end: windows [0, pair_end) may take the tile loop two sub-tiles at a time, the others
+  // take one at a time whatever the split (the two differ in fp32 rounding: attn_tbl_tiles).  A
+  // launch over several levels (wf_window_attention_fwd_levels) gives each level the form its
+  // own launch would have taken, so its bits do not move.
+  using namespace tbl;
   constexpr bool SPLIT = P == PREC_SPLIT;  // P: Prec (operand kind)
-  constexpr int N = 512, HD = 16;
-  constexpr int TBLN = 547;      // reachable rows of the (15^3, heads) table under Q2
-  constexpr int KS = 32;         // K row: hi[16] | lo[16], chunks swizzled (kswz)
-  // V: [hi, lo][key/4][hd][4 keys], each key-quad block padded to 136 B so the staging
-  // stores (lanes 64 / 128 B apart) spread over the banks; the loop's 16-lane reads stay
-  // contiguous inside one block
-  constexpr int VB = HD * 4 + 4;
-  constexpr int VQ = (N / 4) * VB;
   // one LDS block, the table first: its quads then sit below the 64-KiB reach of the ds_read
   // offset field, so a tile's 4 bias reads are one base register + immediates (separate
   // __shared__ arrays were placed table-last, 72 KB up: one address add per read)
-#if WF_ATTN_T4
-  // the reversed table as overlapping quads: tq[i] = {tbr[i], tbr[i+1], tbr[i+2], tbr[i+3]},
-  // so a lane's 4 consecutive bias values are one aligned ds_read_b128
-  constexpr int TQ_BYTES = TBLN * 16;
-#else
-  constexpr int TQ_BYTES = ((TBLN + 1) * 4 + 15) / 16 * 16;
-#endif
   __shared__ __attribute__((aligned(16))) uint8_t lds_tbl[TQ_BYTES + N * KS * 2 + 2 * VQ * 2];
-#if WF_ATTN_T4
   f32x4* tq = reinterpret_cast<f32x4*>(lds_tbl);
-#else
-  float* tbr = reinterpret_cast<float*>(lds_tbl);  // reversed, x log2 e
-#endif
   uint16_t* Ks = reinterpret_cast<uint16_t*>(lds_tbl + TQ_BYTES);
   uint16_t* Vq = Ks + N * KS;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int tid = threadIdx.x;
   int qs, h;
   int64_t bw;
   attn_block(qsplit, heads, qs, h, bw);
@@ -386,9 +481,7 @@ __global__ __launch_bounds__(512, 2) void attn_tbl_kernel(const void* __restrict
   const int64_t row0 = bw * N;
   const bf16x8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
 
-  for (int i = tid; i < TBLN; i += 512)
-#if WF_ATTN_T4
-  {
+  for (int i = tid; i < TBLN; i += 512) {
     // tq[j].c = tbr[j + c] = table[TBLN - 1 - j - c] (0 past the end: never read)
     const float v = table[(int64_t)i * heads + h] * 1.4426950408889634f;
     const int j = TBLN - 1 - i;
@@ -398,9 +491,6 @@ __global__ __launch_bounds__(512, 2) void attn_tbl_kernel(const void* __restrict
     if (j >= TBLN - 3)
       for (int c = TBLN - j; c < 4; ++c) reinterpret_cast<float*>(&tq[j])[c] = 0.f;
   }
-#else
-    tbr[TBLN - 1 - i] = table[(int64_t)i * heads + h] * 1.4426950408889634f;
-#endif
   for (int it = tid; it < N * 2; it += 512) {  // K: (key, 8-value chunk)
     const int key = it >> 1, ch = it & 1, sw = kswz(key);
     bf16x8 hi = z8, lo = z8;
@@ -426,322 +516,12 @@ __global__ __launch_bounds__(512, 2) void attn_tbl_kernel(const void* __restrict
   }
   __syncthreads();
 
-  const int l15 = lane & 15, g4 = lane >> 4;
-  const int kch = 8 * (g4 ^ kswz(l15));  // this lane's K chunk (rows t*64 + kt*16 + l15)
-  const short one = (short)op_cvt<P>(1.0f);
-  const bf16x8 ones = bf16x8{one, one, one, one, one, one, one, one};
   const int nsub = N / 16 / qsplit;  // 16-query sub-tiles of this workgroup
-#if WF_ATTN_QP
-  static_assert(WF_ATTN_LAZY && WF_ATTN_MFMA_SUM && WF_ATTN_T4 && WF_ATTN_BPERMUTE,
-                "the query-pair loop implements the default options only");
-  // WF_ATTN_QP_VSUM (split operands): the row sums as fp32 VALU adds of the exponentials (each
-  // lane's partial over its 4 keys per 16-key block, the 4 lanes of a query reduced once at
-  // the end) instead of the ones-operand MFMAs (4 of 18 per tile and sub-tile): 157.0 vs
-  // 159.6 us per B = 8 stage-1 launch, interleaved (profiles/r6/r6n_attn_vsum_ab.txt).  The
-  // sum is then of the fp32 exponentials rather than of their hi + lo splits (closer to exact
-  // by the split's 2^-16 residual).  Plain bf16 / fp16 keep the MFMA sums: their l must be
-  // the sum of the same rounded P the numerator uses.
-  constexpr bool VSUM = WF_ATTN_QP_VSUM && SPLIT;
-  if (nsub >= 16 && bw < pair_end) {
-    // two independent 16-query sub-tiles per wave (st and st + 8): every K / V fragment read
-    // from LDS feeds both, and the two sub-tiles' dependency chains (scores -> max -> exp ->
-    // PV) interleave -- the single-sub-tile loop left the SIMDs waiting on those chains with
-    // four waves each (LDS caps the workgroups at two per CU)
-    constexpr int NQ = 2;
-    for (int st = wid; st < nsub; st += 8 * NQ) {
-      int qq[NQ], rbq[NQ];
-      bf16x8 b1[NQ], b2[NQ];
-      f32x4 o[NQ], l4[NQ];
-      float mrun[NQ];
-#pragma unroll
-      for (int u = 0; u < NQ; ++u) {
-        const int q = qs * (N / qsplit) + (st + 8 * u) * 16 + l15;
-        qq[u] = q;
-        bf16x8 hi = z8, lo = z8;
-        load8_split_scaled<P>(qkv, (row0 + q) * ld + h * HD + 8 * (g4 & 1), scale_log2, hi, lo);
-        b1[u] = hi;
-        b2[u] = (SPLIT && g4 < 2) ? lo : z8;
-        const int qz = q >> 6, qy = (q >> 3) & 7, qx = q & 7;
-        rbq[u] = (TBLN - 1) - ((qz + 7) * 23 + (qy + 7) * 15 + (qx + 7)) +
-                 ((g4 >> 1) * 15 + 4 * (g4 & 1));
-        o[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-        l4[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-        mrun[u] = -INFINITY;
-      }
-      for (int t = 0; t < 8; ++t) {
-        f32x4 s[NQ][4];
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt) {
-          const bf16x8 a = *reinterpret_cast<const bf16x8*>(&Ks[(t * 64 + kt * 16 + l15) * KS + kch]);
-#pragma unroll
-          for (int u = 0; u < NQ; ++u) {
-            s[u][kt] = mma32<P>(a, b1[u], tq[rbq[u] + 23 * t + 30 * kt]);
-            if (SPLIT) s[u][kt] = mma32<P>(a, b2[u], s[u][kt]);
-          }
-        }
-        float lmax[NQ];
-        bool big = false;
-#pragma unroll
-        for (int u = 0; u < NQ; ++u) {
-          lmax[u] = s[u][0][0];
-#pragma unroll
-          for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-            for (int i = (kt == 0 ? 1 : 0); i < 4; ++i) lmax[u] = fmaxf(lmax[u], s[u][kt][i]);
-          big = big || lmax[u] > mrun[u] + WF_ATTN_TAU;
-        }
-        if (__builtin_amdgcn_ballot_w64(big) != 0) {  // wave-uniform
-#pragma unroll
-          for (int u = 0; u < NQ; ++u) {
-            float tmax = fmaxf(mrun[u], lmax[u]);
-            tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
-            tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-            const float alpha = __builtin_amdgcn_exp2f(mrun[u] - tmax);  // 0 on the first tile
-            mrun[u] = tmax;
-            o[u] *= alpha;
-            l4[u] *= alpha;
-          }
-        }
-        uint32_t ph[NQ][4][2], pl[NQ][4][2];
-#pragma unroll
-        for (int u = 0; u < NQ; ++u)
-#pragma unroll
-          for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-            for (int i = 0; i < 4; i += 2) {
-              const float e0 = __builtin_amdgcn_exp2f(s[u][kt][i] - mrun[u]);
-              const float e1 = __builtin_amdgcn_exp2f(s[u][kt][i + 1] - mrun[u]);
-              if (VSUM) l4[u][0] += e0 + e1;
-              split_pair<P>(e0, e1, ph[u][kt][i >> 1], pl[u][kt][i >> 1]);
-            }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int o1 = (16 * t + 8 * j + g4) * VB + l15 * 4;
-          const int o2 = (16 * t + 8 * j + 4 + g4) * VB + l15 * 4;
-          const bf16x4 v1 = *reinterpret_cast<const bf16x4*>(&Vq[o1]);
-          const bf16x4 v2 = *reinterpret_cast<const bf16x4*>(&Vq[o2]);
-          const bf16x8 vh = bf16x8{v1[0], v1[1], v1[2], v1[3], v2[0], v2[1], v2[2], v2[3]};
-          bf16x8 vl = z8;
-          if (SPLIT) {
-            const bf16x4 w1 = *reinterpret_cast<const bf16x4*>(&Vq[VQ + o1]);
-            const bf16x4 w2 = *reinterpret_cast<const bf16x4*>(&Vq[VQ + o2]);
-            vl = bf16x8{w1[0], w1[1], w1[2], w1[3], w2[0], w2[1], w2[2], w2[3]};
-          }
-#pragma unroll
-          for (int u = 0; u < NQ; ++u) {
-            const bf16x8 pb = __builtin_bit_cast(
-                bf16x8, u32x4{ph[u][2 * j][0], ph[u][2 * j][1], ph[u][2 * j + 1][0], ph[u][2 * j + 1][1]});
-            if (SPLIT) {
-              const bf16x8 plb = __builtin_bit_cast(
-                  bf16x8, u32x4{pl[u][2 * j][0], pl[u][2 * j][1], pl[u][2 * j + 1][0], pl[u][2 * j + 1][1]});
-              o[u] = mma32<P>(vl, pb, o[u]);
-              o[u] = mma32<P>(vh, plb, o[u]);
-              if (!VSUM) l4[u] = mma32<P>(ones, plb, l4[u]);
-            }
-            o[u] = mma32<P>(vh, pb, o[u]);
-            if (!VSUM) l4[u] = mma32<P>(ones, pb, l4[u]);
-          }
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < NQ; ++u) {
-        if (VSUM) {  // the 4 lanes (g4) of query l15
-          l4[u][0] += __shfl_xor(l4[u][0], 16, 64);
-          l4[u][0] += __shfl_xor(l4[u][0], 32, 64);
-        }
-        const float inv = 1.f / l4[u][0];
-        const int64_t off = (row0 + qq[u]) * C + h * HD + 4 * g4;
-        if (store32(P)) {
-          *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(out) + off) = o[u] * inv;
-        } else {
-          bf16x4 r;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) r[i] = (short)f2bf(o[u][i] * inv);
-          *reinterpret_cast<bf16x4*>(reinterpret_cast<uint16_t*>(out) + off) = r;
-        }
-      }
-    }
-    return;
-  }
-#endif
-  // the query-pair loop's VALU row sums, in the same order, wherever it runs (the qsplit = 4
-  // launches of small grids take this loop: a volume's result must not depend on the batch)
-  constexpr bool VSUM1 = WF_ATTN_QP && WF_ATTN_QP_VSUM && SPLIT && WF_ATTN_MFMA_SUM && WF_ATTN_LAZY;
-  for (int st = wid; st < nsub; st += 8) {
-    const int q = qs * (N / qsplit) + st * 16 + l15;
-    // B operands of S: slots 8 g4 .. +7 <- Q'[q][8 (g4 & 1) ..]: [Q'h | Q'h] and [Q'l | 0]
-    bf16x8 b1 = z8, b2 = z8;
-    {
-      bf16x8 hi = z8, lo = z8;
-      load8_split_scaled<P>(qkv, (row0 + q) * ld + h * HD + 8 * (g4 & 1), scale_log2, hi, lo);
-      b1 = hi;
-      b2 = (SPLIT && g4 < 2) ? lo : z8;
-    }
-    const int qz = q >> 6, qy = (q >> 3) & 7, qx = q & 7;
-    // reversed-table base of tile 0: (TBLN - 1) - index(q, key (0, 2 (g4 >> 1), 4 (g4 & 1)))
-    const int rb = (TBLN - 1) - ((qz + 7) * 23 + (qy + 7) * 15 + (qx + 7)) +
-                   ((g4 >> 1) * 15 + 4 * (g4 & 1));
-    f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
-#if WF_ATTN_MFMA_SUM
-    f32x4 l4 = f32x4{0.f, 0.f, 0.f, 0.f};
-#else
-    float lsum = 0.f;  // this lane's 16 keys of each tile; the 4 key groups are summed at the end
-#endif
-    float mrun = -INFINITY;
-    // S^T of 64-key tile t: 4 sub-tiles of 16 keys, the accumulator starting at the bias
-    auto scores = [&](int t, f32x4 (&s)[4]) {
-#if WF_ATTN_T4
-      const f32x4* bq = tq + rb + 23 * t;
-#else
-      const float* bt = tbr + rb + 23 * t;
-#endif
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt) {
-        const bf16x8 a = *reinterpret_cast<const bf16x8*>(&Ks[(t * 64 + kt * 16 + l15) * KS + kch]);
-#if WF_ATTN_T4
-        const f32x4 bias = bq[30 * kt];
-#else
-        const f32x4 bias = f32x4{bt[30 * kt], bt[30 * kt + 1], bt[30 * kt + 2], bt[30 * kt + 3]};
-#endif
-        s[kt] = mma32<P>(a, b1, bias);
-        if (SPLIT) s[kt] = mma32<P>(a, b2, s[kt]);
-      }
-    };
-#pragma unroll 2
-    for (int t = 0; t < 8; ++t) {  // 64-key tiles (one z slice of the window each)
-      f32x4 s[4];
-      scores(t, s);
-#if WF_ATTN_LAZY
-      float lmax = s[0][0];  // a chain, so the compiler pairs it into v_max3_f32
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int i = (kt == 0 ? 1 : 0); i < 4; ++i) lmax = fmaxf(lmax, s[kt][i]);
-      if (__builtin_amdgcn_ballot_w64(lmax > mrun + WF_ATTN_TAU) != 0) {  // wave-uniform
-        float tmax = fmaxf(mrun, lmax);
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-        const float alpha = __builtin_amdgcn_exp2f(mrun - tmax);  // 0 on the first tile
-        mrun = tmax;
-        o *= alpha;
-#if WF_ATTN_MFMA_SUM
-        l4 *= alpha;
-#else
-        lsum *= alpha;
-#endif
-      }
-      const float mnew = mrun;
-#else
-      float tmax = mrun;  // a chain, so the compiler pairs it into v_max3_f32
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) tmax = fmaxf(tmax, s[kt][i]);
-#if WF_ATTN_BPERMUTE
-      tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
-      tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-#else
-      // the 4 key groups of a query column (lanes l15 + 16 g4): xor 16 / xor 32 exchanges on
-      // v_permlane16_swap / v_permlane32_swap (VALU) instead of two ds_bpermute round trips
-      // on every tile's max -> exp chain
-      {
-        const auto r16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(tmax),
-                                                          __float_as_uint(tmax), false, false);
-        tmax = fmaxf(__uint_as_float(r16[0]), __uint_as_float(r16[1]));
-        const auto r32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(tmax),
-                                                          __float_as_uint(tmax), false, false);
-        tmax = fmaxf(__uint_as_float(r32[0]), __uint_as_float(r32[1]));
-      }
-#endif
-      const float mnew = tmax;
-      const float alpha = __builtin_amdgcn_exp2f(mrun - mnew);
-      mrun = mnew;
-      o *= alpha;
-#if WF_ATTN_MFMA_SUM
-      l4 *= alpha;
-#else
-      lsum *= alpha;
-#endif
-#endif  // WF_ATTN_LAZY
-      // P^T operand words: pairs of 16-bit values, hi and (bf16x3) lo parts
-      uint32_t ph[4][2], pl[4][2];
-#if !WF_ATTN_MFMA_SUM
-      float ps[4];
-#endif
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt) {
-#pragma unroll
-        for (int i = 0; i < 4; i += 2) {
-          const float p0 = __builtin_amdgcn_exp2f(s[kt][i] - mnew);
-          const float p1 = __builtin_amdgcn_exp2f(s[kt][i + 1] - mnew);
-#if WF_ATTN_MFMA_SUM
-          if (VSUM1) l4[0] += p0 + p1;
-#endif
-          if (WF_ATTN_DOT2) {
-            split_pair<P>(p0, p1, ph[kt][i >> 1], pl[kt][i >> 1]);
-          } else {
-            const uint16_t hb0 = op_cvt<P>(p0), hb1 = op_cvt<P>(p1);
-            ph[kt][i >> 1] = (uint32_t)hb0 | ((uint32_t)hb1 << 16);
-            pl[kt][i >> 1] = (uint32_t)(uint16_t)op_lo<P>(p0, hb0) |
-                             ((uint32_t)(uint16_t)op_lo<P>(p1, hb1) << 16);
-          }
-#if !WF_ATTN_MFMA_SUM
-          ps[i] = kt == 0 ? p0 : ps[i] + p0;  // 4 chains over the key sub-tiles
-          ps[i + 1] = kt == 0 ? p1 : ps[i + 1] + p1;
-#endif
-        }
-      }
-#if !WF_ATTN_MFMA_SUM
-      lsum += (ps[0] + ps[1]) + (ps[2] + ps[3]);
-#endif
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const bf16x8 pb = __builtin_bit_cast(
-            bf16x8, u32x4{ph[2 * j][0], ph[2 * j][1], ph[2 * j + 1][0], ph[2 * j + 1][1]});
-        const int o1 = (16 * t + 8 * j + g4) * VB + l15 * 4;
-        const int o2 = (16 * t + 8 * j + 4 + g4) * VB + l15 * 4;
-        const bf16x4 v1 = *reinterpret_cast<const bf16x4*>(&Vq[o1]);
-        const bf16x4 v2 = *reinterpret_cast<const bf16x4*>(&Vq[o2]);
-        const bf16x8 vh = bf16x8{v1[0], v1[1], v1[2], v1[3], v2[0], v2[1], v2[2], v2[3]};
-        if (SPLIT) {
-          const bf16x8 plb = __builtin_bit_cast(
-              bf16x8, u32x4{pl[2 * j][0], pl[2 * j][1], pl[2 * j + 1][0], pl[2 * j + 1][1]});
-          const bf16x4 w1 = *reinterpret_cast<const bf16x4*>(&Vq[VQ + o1]);
-          const bf16x4 w2 = *reinterpret_cast<const bf16x4*>(&Vq[VQ + o2]);
-          const bf16x8 vl = bf16x8{w1[0], w1[1], w1[2], w1[3], w2[0], w2[1], w2[2], w2[3]};
-          o = mma32<P>(vl, pb, o);
-          o = mma32<P>(vh, plb, o);
-#if WF_ATTN_MFMA_SUM
-          if (!VSUM1) l4 = mma32<P>(ones, plb, l4);
-#endif
-        }
-        o = mma32<P>(vh, pb, o);
-#if WF_ATTN_MFMA_SUM
-        if (!VSUM1) l4 = mma32<P>(ones, pb, l4);
-#endif
-      }
-    }
-#if WF_ATTN_MFMA_SUM
-    if (VSUM1) {  // the 4 lanes (g4) of query l15, as in the query-pair loop
-      l4[0] += __shfl_xor(l4[0], 16, 64);
-      l4[0] += __shfl_xor(l4[0], 32, 64);
-    }
-    const float inv = 1.f / l4[0];
-#else
-    lsum = xsum16(lsum);
-    lsum = xsum32(lsum);
-    const float inv = 1.f / lsum;
-#endif
-    const int64_t off = (row0 + q) * C + h * HD + 4 * g4;
-    if (store32(P)) {
-      *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(out) + off) = o * inv;
-    } else {
-      bf16x4 r;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) r[i] = (short)f2bf(o[i] * inv);
-      *reinterpret_cast<bf16x4*>(reinterpret_cast<uint16_t*>(out) + off) = r;
-    }
-  }
+  const int q0 = qs * (N / qsplit);
+  if (nsub >= 16 && bw < pair_end)
+    attn_tbl_tiles<P, 2>(qkv, out, tq, Ks, Vq, row0, q0, h, heads, nsub, scale_log2);
+  else
+    attn_tbl_tiles<P, 1>(qkv, out, tq, Ks, Vq, row0, q0, h, heads, nsub, scale_log2);
 }
 
 bool attn_tbl_pair_loop(int64_t wh) { return wh >= 256; }
@@ -760,26 +540,19 @@ int launch_attn_core(const void* qkv, const float* bias, void* out, float* lse, 
   if (table_ws) {  // bias = the (T, heads) table; index from the coordinates
     if (table_ws != 8 || hd != 16 || N != 512)
       return fail(WF_E_SHAPE, "attention (table bias): implemented for ws = 8, head_dim = 16");
-    if (!lse) {
-      // queries of one (window, head) split over 1, 2 or 4 workgroups: enough workgroups for
-      // two per CU, each staging the window's K / V once
-      const int64_t wh = Bw * heads;
-      const int qsplit = wh >= 512 ? 1 : (attn_tbl_pair_loop(wh) ? 2 : 4);
-      const dim3 g1((unsigned)(wh * qsplit));
-      auto k = split ? attn_tbl_kernel<PREC_SPLIT>
-                     : (f16 ? attn_tbl_kernel<PREC_FP16> : attn_tbl_kernel<PREC_BF16>);
-      const int64_t pair_end = pair_windows < 0 ? Bw : pair_windows;
-      hipLaunchKernelGGL(k, g1, dim3(512), 0, s, qkv, bias, out, heads, qsplit, sl2, pair_end);
-      return check_launch("attention core (table bias, window per workgroup)");
-    }
-    // training (lse): the tiled kernel
-    auto k = split ? attn_core_kernel<16, 64, PREC_SPLIT, 8>
-                   : (f16 ? attn_core_kernel<16, 64, PREC_FP16, 8>
-                          : attn_core_kernel<16, 64, PREC_BF16, 8>);
-    hipLaunchKernelGGL(k, grid, dim3(256), 0, s, qkv, bias, out, lse, N, heads, sl2);
-    return check_launch("attention core (table bias)");
+    if (lse) return fail(WF_E_SHAPE, "attention (table bias): inference only, no log-sum-exp");
+    // queries of one (window, head) split over 1, 2 or 4 workgroups: enough workgroups for
+    // two per CU, each staging the window's K / V once
+    const int64_t wh = Bw * heads;
+    const int qsplit = wh >= 512 ? 1 : (attn_tbl_pair_loop(wh) ? 2 : 4);
+    const dim3 g1((unsigned)(wh * qsplit));
+    auto k = split ? attn_tbl_kernel<PREC_SPLIT>
+                   : (f16 ? attn_tbl_kernel<PREC_FP16> : attn_tbl_kernel<PREC_BF16>);
+    const int64_t pair_end = pair_windows < 0 ? Bw : pair_windows;
+    hipLaunchKernelGGL(k, g1, dim3(512), 0, s, qkv, bias, out, heads, qsplit, sl2, pair_end);
+    return check_launch("attention core (table bias, window per workgroup)");
   }
-#define WF_ATTN_CASE(HDV)                                                                  \
+#define ATTN_HD_CASE(HDV)                                                                  \
   case HDV: {                                                                              \
     auto k = split ? attn_core_kernel<HDV, (HDV >= 192 ? 32 : 64), PREC_SPLIT>             \
                    : (f16 ? attn_core_kernel<HDV, 64, PREC_FP16>                           \
@@ -788,18 +561,18 @@ int launch_attn_core(const void* qkv, const float* bias, void* out, float* lse, 
     break;                                                                                 \
   }
   switch (hd) {
-    WF_ATTN_CASE(16)
-    WF_ATTN_CASE(32)
-    WF_ATTN_CASE(48)
-    WF_ATTN_CASE(64)
-    WF_ATTN_CASE(96)
-    WF_ATTN_CASE(128)
-    WF_ATTN_CASE(192)
-    WF_ATTN_CASE(384)
+    ATTN_HD_CASE(16)
+    ATTN_HD_CASE(32)
+    ATTN_HD_CASE(48)
+    ATTN_HD_CASE(64)
+    ATTN_HD_CASE(96)
+    ATTN_HD_CASE(128)
+    ATTN_HD_CASE(192)
+    ATTN_HD_CASE(384)
     default:
       return fail(WF_E_SHAPE, "attention: head_dim must be one of 16,32,48,64,96,128,192,384");
   }
-#undef WF_ATTN_CASE
+#undef ATTN_HD_CASE
   return check_launch("attention core");
 }
 
@@ -811,7 +584,72 @@ __global__ void rel_pos_bias_kernel(const float* __restrict__ table, const int64
   for (int h = 0; h < heads; ++h) bias[h * NN + i] = table[r * heads + h];
 }
 
-static int64_t act_bytes(int prec) { return store32(prec) ? 4 : 2; }
+// The workspace of a forward over `rows` tokens: qkv (rows, 3 C) at offset 0, the core's output
+// (rows, C) at `ao`, both in the precision's activation storage and 256-B aligned.
+struct AttnWorkspace {
+  int64_t ao, bytes;
+};
+static AttnWorkspace attn_workspace(int64_t rows, int64_t C, int prec) {
+  const int64_t e = store32(prec) ? 4 : 2;
+  const int64_t ao = align256(rows * 3 * C * e);
+  return {ao, ao + align256(rows * C * e)};
+}
+
+// qkv = Linear(window_partition(norm1?(x))) of a (B, D1, H1, W1, C) raster into (rows, 3 C)
+static GemmArgs qkv_gemm_args(const float* x, const float* ln_w, const float* ln_b, float ln_eps,
+                              const uint16_t* wqkv, const float* bqkv, void* qkv, int64_t rows,
+                              int64_t B, int64_t C, int64_t D1, int64_t H1, int64_t W1,
+                              int64_t ws, int prec) {
+  GemmArgs g{};
+  g.prec = prec;
+  g.a_src = x;
+  g.a_bf16 = 0;
+  g.a_C = (int)C;
+  g.a_nseg = 1;
+  g.a_map = MAP_WINDOW;
+  g.mB = (int)B;
+  g.mD = (int)D1;
+  g.mH = (int)H1;
+  g.mW = (int)W1;
+  g.mws = (int)ws;
+  g.a_ln = ln_w ? LN_COMPUTE : LN_NONE;
+  g.a_ln_w = ln_w;
+  g.a_ln_b = ln_b;
+  g.a_eps = ln_eps;
+  g.w = wqkv;
+  g.M = rows;
+  g.N = (int)(3 * C);
+  g.K = (int)C;
+  g.epi = EPI_STORE;
+  g.bias = bqkv;
+  g.out = qkv;
+  g.out_bf16 = !store32(prec);
+  g.ldo = 3 * C;
+  return g;
+}
+
+// out = Linear(core output); window-major rows == the reshaped raster (Q1)
+static GemmArgs proj_gemm_args(const void* ao, const uint16_t* wproj, const float* bproj,
+                               float* out, int64_t rows, int64_t C, int prec) {
+  GemmArgs p{};
+  p.prec = prec;
+  p.a_src = ao;
+  p.a_bf16 = !store32(prec);
+  p.a_C = (int)C;
+  p.a_nseg = 1;
+  p.a_map = MAP_IDENTITY;
+  p.a_ln = LN_NONE;
+  p.w = wproj;
+  p.M = rows;
+  p.N = (int)C;
+  p.K = (int)C;
+  p.epi = EPI_STORE;
+  p.bias = bproj;
+  p.out = out;
+  p.out_bf16 = 0;
+  p.ldo = C;
+  return p;
+}
 
 }  // namespace wf
 
@@ -831,11 +669,7 @@ extern "C" int wf_rel_pos_bias(const float* table, const int64_t* index, float* 
 
 extern "C" int64_t wf_window_attention_workspace_bytes(int64_t B, int64_t C, int64_t D1,
                                                        int64_t H1, int64_t W1, int precision) {
-  const int64_t rows = B * D1 * H1 * W1;
-  const int64_t e = act_bytes(precision);
-  const int64_t qkv = ((rows * 3 * C * e) + 255) & ~(int64_t)255;
-  const int64_t ao = ((rows * C * e) + 255) & ~(int64_t)255;
-  return qkv + ao;
+  return attn_workspace(B * D1 * H1 * W1, C, precision).bytes;
 }
 
 static int window_attention_impl(const float* x, const float* ln_w, const float* ln_b,
@@ -860,62 +694,21 @@ static int window_attention_impl(const float* x, const float* ln_w, const float*
   const int64_t N = ws * ws * ws;
   const int64_t rows = B * D1 * H1 * W1;
   const int64_t Bw = rows / N;
-  const int64_t e = act_bytes(precision);
   hipStream_t s = (hipStream_t)stream;
   void* qkv = workspace;
-  void* ao = reinterpret_cast<char*>(workspace) + (((rows * 3 * C * e) + 255) & ~(int64_t)255);
-  const int obf = !store32(precision);
+  void* ao = reinterpret_cast<char*>(workspace) + attn_workspace(rows, C, precision).ao;
   // 1. qkv = Linear(window_partition(norm1?(x)))
-  GemmArgs g{};
-  g.prec = precision;
-  g.a_src = x;
-  g.a_bf16 = 0;
-  g.a_C = (int)C;
-  g.a_nseg = 1;
-  g.a_map = MAP_WINDOW;
-  g.mB = (int)B;
-  g.mD = (int)D1;
-  g.mH = (int)H1;
-  g.mW = (int)W1;
-  g.mws = (int)ws;
-  g.a_ln = ln_w ? LN_COMPUTE : LN_NONE;
-  g.a_ln_w = ln_w;
-  g.a_ln_b = ln_b;
-  g.a_eps = ln_eps;
-  g.w = wqkv_bf16x2;
-  g.M = rows;
-  g.N = (int)(3 * C);
-  g.K = (int)C;
-  g.epi = EPI_STORE;
-  g.bias = bqkv;
-  g.out = qkv;
-  g.out_bf16 = obf;
-  g.ldo = 3 * C;
-  int rc = launch_gemm(g, s, "wf_window_attention_fwd(qkv)");
+  int rc = launch_gemm(qkv_gemm_args(x, ln_w, ln_b, ln_eps, wqkv_bf16x2, bqkv, qkv, rows, B, C,
+                                     D1, H1, W1, ws, precision),
+                       s, "wf_window_attention_fwd(qkv)");
   if (rc) return rc;
   // 2. softmax(q k^T * scale + bias) v
   rc = launch_attn_core(qkv, bias, ao, lse, Bw, (int)N, (int)heads, (int)(C / heads), scale,
                         precision, s, table_ws);
   if (rc) return rc;
   // 3. proj; window-major rows == the reshaped raster (Q1)
-  GemmArgs p{};
-  p.prec = precision;
-  p.a_src = ao;
-  p.a_bf16 = obf;
-  p.a_C = (int)C;
-  p.a_nseg = 1;
-  p.a_map = MAP_IDENTITY;
-  p.a_ln = LN_NONE;
-  p.w = wproj_bf16x2;
-  p.M = rows;
-  p.N = (int)C;
-  p.K = (int)C;
-  p.epi = EPI_STORE;
-  p.bias = bproj;
-  p.out = out;
-  p.out_bf16 = 0;
-  p.ldo = C;
-  return launch_gemm(p, s, "wf_window_attention_fwd(proj)");
+  return launch_gemm(proj_gemm_args(ao, wproj_bf16x2, bproj, out, rows, C, precision), s,
+                     "wf_window_attention_fwd(proj)");
 }
 
 extern "C" int wf_window_attention_fwd_train(const float* x, const float* ln_w,
@@ -970,8 +763,7 @@ extern "C" int64_t wf_window_attention_levels_workspace_bytes(const int64_t* dhw
                                                               int precision) {
   AttnLevels L;
   if (attn_levels_plan(dhw, nlev, B, C, C / 16, L)) return WF_E_SHAPE;
-  const int64_t rows = L.row0[nlev], e = act_bytes(precision);
-  return (((rows * 3 * C * e) + 255) & ~(int64_t)255) + (((rows * C * e) + 255) & ~(int64_t)255);
+  return attn_workspace(L.row0[nlev], C, precision).bytes;
 }
 
 extern "C" int wf_window_attention_fwd_levels(const float* const* x, const int64_t* dhw, int nlev,
@@ -996,20 +788,13 @@ extern "C" int wf_window_attention_fwd_levels(const float* const* x, const int64
   WF_REQUIRE_PTR(workspace);
   constexpr int64_t ws = kAttnLevelsWs, N = ws * ws * ws;
   const int64_t rows = L.row0[nlev];
-  const int64_t e = act_bytes(precision);
   hipStream_t s = (hipStream_t)stream;
   void* qkv = workspace;
-  void* ao = reinterpret_cast<char*>(workspace) + (((rows * 3 * C * e) + 255) & ~(int64_t)255);
-  const int obf = !store32(precision);
-  // 1. qkv = Linear(window_partition(x_l)) of every level
-  GemmArgs g{};
-  g.prec = precision;
-  g.a_src = x[0];
-  g.a_C = (int)C;
-  g.a_nseg = 1;
+  void* ao = reinterpret_cast<char*>(workspace) + attn_workspace(rows, C, precision).ao;
+  // 1. qkv = Linear(window_partition(x_l)) of every level: the rows' sources come from lv_*
+  GemmArgs g = qkv_gemm_args(x[0], nullptr, nullptr, 0.f, wqkv_bf16x2, bqkv, qkv, rows, B, C, 0,
+                             0, 0, ws, precision);
   g.a_map = MAP_LEVELS;
-  g.mB = (int)B;
-  g.mws = (int)ws;
   for (int l = 0; l < WF_MAX_LEVELS; ++l) {
     const bool on = l < nlev;
     g.lv_src[l] = on ? x[l] : x[0];
@@ -1018,16 +803,6 @@ extern "C" int wf_window_attention_fwd_levels(const float* const* x, const int64
     g.lv_H[l] = on ? L.H[l] : (int)ws;
     g.lv_W[l] = on ? L.W[l] : (int)ws;
   }
-  g.a_ln = LN_NONE;
-  g.w = wqkv_bf16x2;
-  g.M = rows;
-  g.N = (int)(3 * C);
-  g.K = (int)C;
-  g.epi = EPI_STORE;
-  g.bias = bqkv;
-  g.out = qkv;
-  g.out_bf16 = obf;
-  g.ldo = 3 * C;
   // the core loop each level's own launch takes (attn_tbl_kernel, pair_end): the merged launch
   // keeps it per level, so the levels on the query-pair loop must come first
   int64_t pair_windows = 0;
@@ -1058,22 +833,6 @@ extern "C" int wf_window_attention_fwd_levels(const float* const* x, const int64
                         precision, s, (int)ws, pair_windows);
   if (rc) return rc;
   // 3. proj; window-major rows, level after level
-  GemmArgs p{};
-  p.prec = precision;
-  p.a_src = ao;
-  p.a_bf16 = obf;
-  p.a_C = (int)C;
-  p.a_nseg = 1;
-  p.a_map = MAP_IDENTITY;
-  p.a_ln = LN_NONE;
-  p.w = wproj_bf16x2;
-  p.M = rows;
-  p.N = (int)C;
-  p.K = (int)C;
-  p.epi = EPI_STORE;
-  p.bias = bproj;
-  p.out = out;
-  p.out_bf16 = 0;
-  p.ldo = C;
-  return launch_gemm(p, s, "wf_window_attention_fwd_levels(proj)");
+  return launch_gemm(proj_gemm_args(ao, wproj_bf16x2, bproj, out, rows, C, precision), s,
+                     "wf_window_attention_fwd_levels(proj)");
 }

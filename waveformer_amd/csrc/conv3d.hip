@@ -31,9 +31,6 @@
 
 namespace wf {
 
-#ifndef WF_C3W_WDMA  // 0: conv3d_k3w stages weights through registers (round-5 form; A/B only)
-#define WF_C3W_WDMA 1
-#endif
 #ifndef WF_CONV_DBG  // 1: timing-experiment build (Conv3Args::dbg phase skips; never the shipped library)
 #define WF_CONV_DBG 0
 #endif
@@ -60,7 +57,8 @@ struct Conv3Args {
   const uint16_t* xh; // XH kernels: the input as fp16 (the operands WF_PREC_FP16 stages; same
                       // positions / ldx as x)
   int dbg;            // WF_CONV_DBG builds: 1 no activation loads, 2 no activation LDS stores,
-                      // 4 no weight loads, 8 no weight LDS stores, 16 no MFMA K loop
+                      // 4 no weight loads, 8 no weight LDS stores (4, 8: conv3d_k3_kernel
+                      // only), 16 no MFMA K loop
 };
 
 // RW output rows per wave (wave w: rows w, w + 4, ...): RW = 2 halves the weight-fragment LDS
@@ -398,8 +396,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_k3w_kernel(Conv3Args a) {
   constexpr int CW = 2 * kConvCC;                    // 16 channels staged per step
   constexpr int PB = CW * 2;                         // 32 B per position
   constexpr int NFRAG = 2 * kConvKS * CO_T;          // 42 weight fragments per step
-  constexpr int NW = WF_C3W_WDMA ? 1 : (NFRAG * 64 + 511) / 512;  // 16-B weight pieces per thread
-  constexpr int NFW = (NFRAG + 7) / 8;               // WDMA: 1-KB fragments per wave
+  constexpr int NFW = (NFRAG + 7) / 8;               // 1-KB weight fragments per wave
   constexpr int QN = XH ? CW / 8 : CW / 4;           // lanes per position (16 B each)
   constexpr int PSTEP = 512 / QN;
   constexpr int NJ = (NPOS * QN + 511) / 512;
@@ -464,7 +461,6 @@ __global__ __launch_bounds__(512, 1) void conv3d_k3w_kernel(Conv3Args a) {
 
   f32x4 sa[XH ? 1 : NJ];
   bf16x8 sah[XH ? NJ : 1];
-  bf16x8 sw[NW];
   // activations of step st (SPLIT: of steps st, st + 1, st even)
   auto fetch_act = [&](int st) {
     // channels past Cin read channel 0 (in range); commit() zeroes them
@@ -491,9 +487,8 @@ __global__ __launch_bounds__(512, 1) void conv3d_k3w_kernel(Conv3Args a) {
   };
   // weight fragments of step st: f = (sub * 7 + step) * CO_T + m for chunks 2 st, 2 st + 1 (a
   // missing second chunk, odd nch, reads the first one's: never used); SPLIT: f = (step * 2 +
-  // plane) * CO_T + m of chunk st, the packed order
-#if WF_C3W_WDMA
-  // weights by LDS-DMA (buffer_load_dwordx4 ... lds, no VGPR destination) into the buffer of
+  // plane) * CO_T + m of chunk st, the packed order.  They go
+  // by LDS-DMA (buffer_load_dwordx4 ... lds, no VGPR destination) into the buffer of
   // step st's parity: wave w copies fragments w, w + 8, ... (1 KB each, lane-linear in both
   // the packed global layout and the LDS image); the buffer was last read by step st - 1's
   // K loop, which every wave left before the barrier that precedes this fetch
@@ -520,37 +515,10 @@ __global__ __launch_bounds__(512, 1) void conv3d_k3w_kernel(Conv3Args a) {
           (uint32_t)((frag * 64 + lane) * 16), 0, 0, 0);
     }
   };
-#else
-  auto fetch_w = [&](int st) {
-#if WF_CONV_DBG
-    if (a.dbg & 4) {
-#pragma unroll
-      for (int w = 0; w < NW; ++w) sw[w] = bf16x8{(short)st, 0, 0, 0, 0, 0, 0, 0};
-      return;
-    }
-#endif
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      const int i = min(tid + 512 * w, NFRAG * 64 - 1);
-      const int f = i >> 6, ln = i & 63;
-      const int m = f % CO_T, ss = f / CO_T;
-      int64_t frag;
-      if constexpr (SPLIT) {
-        frag = ((int64_t)st * kConvKS * 2 + ss) * cblk + co0 / 16 + m;
-      } else {
-        const int sub = ss / kConvKS, step = ss - sub * kConvKS;
-        const int ch = min(2 * st + sub, a.nch - 1);
-        frag = ((int64_t)(ch * kConvKS + step) * 2) * cblk + co0 / 16 + m;
-      }
-      sw[w] = *reinterpret_cast<const bf16x8*>(a.w + (frag * 64 + ln) * 8);
-    }
-  };
-#endif
   auto fetch = [&](int st) {
-    // WDMA: the weights first, so the wait for the activations (issued after) covers them
-    if (WF_C3W_WDMA) fetch_w(st);
+    // the weights first, so the wait for the activations (issued after) covers them
+    fetch_w(st);
     if (!SPLIT || (st & 1) == 0) fetch_act(st);
-    if (!WF_C3W_WDMA) fetch_w(st);
   };
   auto commit = [&](int st) {
     const int c = (SPLIT ? st / 2 : st) * CW + (XH ? 8 : 4) * q;
@@ -558,9 +526,9 @@ __global__ __launch_bounds__(512, 1) void conv3d_k3w_kernel(Conv3Args a) {
     // SPLIT: this step's chunk is held by lanes q >> 1 == st & 1 (uniform per 2 lanes)
     const bool mine = !SPLIT || (q >> 1) == (st & 1);
 #if WF_CONV_DBG
-    const bool skip_a = a.dbg & 2, skip_w = a.dbg & 8;
+    const bool skip_a = a.dbg & 2;
 #else
-    constexpr bool skip_a = false, skip_w = false;
+    constexpr bool skip_a = false;
 #endif
 #pragma unroll
     for (int j = 0; j < NJ && !skip_a; ++j) {
@@ -586,18 +554,8 @@ __global__ __launch_bounds__(512, 1) void conv3d_k3w_kernel(Conv3Args a) {
         *reinterpret_cast<bf16x4*>(s_act + paddr(pos) + 8 * q) = h;
       }
     }
-#if WF_C3W_WDMA
-    (void)skip_w;
     // this wave's weight DMA has landed (the barrier after commit makes every wave's visible)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
-#pragma unroll
-    for (int w = 0; w < NW && !skip_w; ++w) {
-      const int i = tid + 512 * w;
-      if (w == NW - 1 && i >= NFRAG * 64) break;
-      *reinterpret_cast<bf16x8*>(s_w + i * 8) = sw[w];
-    }
-#endif
   };
   const char* lw0 = reinterpret_cast<const char*>(s_w) + lane * 16;
 
@@ -607,7 +565,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_k3w_kernel(Conv3Args a) {
     commit(st);
     __syncthreads();
     if (st + 1 < nst) fetch(st + 1);
-    const char* lw = lw0 + (WF_C3W_WDMA ? (st & 1) * NFRAG * 1024 : 0);
+    const char* lw = lw0 + (st & 1) * NFRAG * 1024;
 #if WF_CONV_DBG
     if (a.dbg & 16) {
       acc[0][0].x += (float)s_act[tid & 63] + (float)lw[0];
@@ -727,9 +685,8 @@ __global__ __launch_bounds__(512, 1) void conv3d_k3w_kernel(Conv3Args a) {
 
 static size_t conv3w_lds() {
   constexpr int NPOS = 3 * 10 * 66;
-  // activations + the weight fragments of one step (WDMA: of two, double-buffered)
-  return (size_t)NPOS * 32 + (NPOS / 8 + 1) * 16 +
-         (size_t)(WF_C3W_WDMA ? 2 : 1) * 2 * kConvKS * 3 * 1024;
+  // activations + the weight fragments of two steps (double-buffered)
+  return (size_t)NPOS * 32 + (NPOS / 8 + 1) * 16 + (size_t)2 * 2 * kConvKS * 3 * 1024;
 }
 
 // out[p][c] = sum_z part[z][p][c], z ascending (the split-K partials, bias in part[0])

@@ -68,10 +68,7 @@ extern "C" int wf_debug_dwfc2tb_probe(long long* host) {
 #endif
 
 namespace tb2 {
-#ifndef WF_TB2_S2
-#define WF_TB2_S2 4
-#endif
-constexpr int S2 = WF_TB2_S2;  // input rows the third D wave of a SIMD scatters between A' and B
+constexpr int S2 = 4;  // input rows the third D wave of a SIMD scatters between A' and B
 constexpr int C = 96, HID = 384, TY = 4, TX = 4;
 constexpr int PY = TY + 2, PX = TX + 2, PP = PY * PX;  // 6 x 6
 constexpr int NPOS = TY * TX;                          // 16

@@ -62,15 +62,9 @@ extern "C" int wf_debug_dwfctb4_probe(long long* host) {
 }
 #endif
 
-#ifndef WF_TB_EPRIO
-#define WF_TB_EPRIO 3
-#endif
-
 namespace tb4 {
-#ifndef WF_TB4_S2
-#define WF_TB4_S2 6
-#endif
-constexpr int S2 = WF_TB4_S2;  // input rows the third D wave of a SIMD scatters in phase 1
+constexpr int EPRIO = 3;  // s_setprio of the fc (E) waves
+constexpr int S2 = 6;  // input rows the third D wave of a SIMD scatters in phase 1
 constexpr int C = 48, HID = 192, TY = 4, TX = 8;
 constexpr int PY = TY + 2, PX = TX + 2, PP = PY * PX;  // 6 x 10
 constexpr int NPOS = TY * TX;                          // 32
@@ -87,10 +81,7 @@ constexpr int NV = HID / 4;
 constexpr int NPC = (PP * NV + 63) / 64;               // 45 LDS-DMA pieces
 static_assert(NPC * 64 == PP * NV, "whole pieces only: the loader issues no partial piece");
 // pieces of a plane the loader issues half an iteration early (part A, see the loader)
-#ifndef WF_TB4_FA
-#define WF_TB4_FA 16
-#endif
-constexpr int FA = WF_TB4_FA;
+constexpr int FA = 16;
 static_assert(FA >= 0 && NPC + FA <= 63, "outstanding pieces must fit the 6-bit vmcnt");
 constexpr int KS = HID / 32;
 constexpr int FWL_BYTES = (C / 16) * KS * 64 * 16;
@@ -334,7 +325,7 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc_tb4_kernel(DwFcArgs a) {
     return;
   }
   // =============================== E0..E2: the fc waves ===================================
-  __builtin_amdgcn_s_setprio(WF_TB_EPRIO);
+  __builtin_amdgcn_s_setprio(EPRIO);
   const int l15 = lane & 15, g4 = lane >> 4;
   const int ct = e;
   const float bs = a.bscale ? a.bscale[b] : 1.f;

@@ -182,7 +182,8 @@ int try_launch_gemm_rows(const GemmArgs& g, hipStream_t s, bool single_chunk_onl
 
 // ---- windowed attention core over a (B_, N, 3C) qkv buffer (bf16, or fp32 when SPLIT) ----
 // table_ws != 0: `bias` is the (T, heads) relative_position_bias_table and the index is the
-// reference's formula for window table_ws (8 with head_dim 16 implemented)
+// reference's formula for window table_ws (8 with head_dim 16 implemented; inference only: a
+// non-null lse is refused)
 // pair_windows (table bias, inference): windows [0, pair_windows) may take the core's
 // query-pair loop, the rest its one-sub-tile loop (< 0: all may); attn_tbl_pair_loop(wh) is the
 // loop a launch of wh (window, head)s takes on its own

@@ -11,8 +11,9 @@
 //   LayerNorm (+ GELU) rows, depthwise 3^3 conv (dgrad = conv with the flipped kernel, wgrad
 //     = per-channel correlation), PatchMerging gather (Q3 duplicates accumulate), PatchEmbed
 //     patch gather, NCDHW -> channel-last transpose (proj_out)
-// The dense GEMM gradients (dX = dY W, dW = dY^T X) are plain library GEMMs (hipBLASLt via
-// torch.mm on the caller's side).  Everything here is fp32 VALU arithmetic: exact enough for
+// The dense GEMM gradients run on this library's own MFMA GEMMs at bf16x3, called from
+// autograd.py: dX = dY W on the streaming GEMM (gemm_rows.hip), dW = dY^T X on wf_gemm_tn
+// (gemm_tn.hip).  Everything here is fp32 VALU arithmetic: exact enough for
 // the fp32 reference's training and free of the split-bf16 bookkeeping.
 #include "kernels.hpp"
 
@@ -996,7 +997,6 @@ int64_t attn_bwd_groups(int64_t Bw, int64_t N, int64_t heads) {
   G = std::min<int64_t>(std::max<int64_t>(G, 1), Bw);
   return cdiv(Bw, cdiv(Bw, G));  // balance: every group gets the same window count (+-1)
 }
-inline int64_t align256(int64_t b) { return (b + 255) & ~(int64_t)255; }
 }  // namespace
 
 extern "C" int64_t wf_window_attention_bwd_workspace_bytes(int64_t B, int64_t C, int64_t D1,

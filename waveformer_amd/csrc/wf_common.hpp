@@ -159,5 +159,6 @@ __device__ __forceinline__ float xsum32(float v) {
 }
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+inline int64_t align256(int64_t b) { return (b + 255) & ~(int64_t)255; }  // workspace sub-buffers
 
 }  // namespace wf

@@ -407,7 +407,7 @@ def window_attn_backward(gout: Tensor, x: Tensor, ln_w: Optional[Tensor],
     rows = B * D1 * H1 * W1
     E = lambda: _empty(x, torch.float32)  # noqa: E731  (outputs may not alias)
     bias = ops.rel_pos_bias(table.detach(), index)
-    qkv_bytes = (rows * 3 * C * 4 + 255) & ~255
+    qkv_bytes = _round256(rows * 3 * C * 4)
     qkv = work[:rows * 3 * C * 4].view(torch.float32).view(rows, 3 * C)
     o = work[qkv_bytes:qkv_bytes + rows * C * 4].view(torch.float32).view(rows, C)
     g = _f32(gout).view(rows, C)
