@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define WF_ABI_VERSION 20
+#define WF_ABI_VERSION 21
 
 enum { WF_PREC_BF16 = 0, WF_PREC_BF16X3 = 1, WF_PREC_FP16 = 2 };
 
@@ -436,7 +436,10 @@ int wf_window_attention_fwd(const float* x, const float* ln_w, const float* ln_b
  * tiling into 8^3 windows.  ws = 8, C = 16 * heads.  out: (sum_l B*D_l*H_l*W_l, C) fp32, level
  * after level, each level window-major exactly as wf_window_attention_fwd_table writes it -- and
  * bitwise what nlev such calls write.  Widths without a multi-level GEMM instantiation run as
- * those nlev calls.  workspace: wf_window_attention_levels_workspace_bytes(...) bytes (the sum
+ * those nlev calls.  At C = 48 with 256 or more (window, head) pairs in the launch there is no
+ * qkv GEMM launch: the core computes q / k / v itself from the rasters and the weight, bitwise
+ * the GEMM's values (wf_window_attention_levels_fused tells), and the qkv part of the workspace
+ * is not written.  wf_window_attention_fwd_table without norm1 takes the same rule.  workspace: wf_window_attention_levels_workspace_bytes(...) bytes (the sum
  * of the per-level sizes; < 0 for an invalid level list), 256-B aligned.                     */
 int64_t wf_window_attention_levels_workspace_bytes(const int64_t* dhw, int nlev, int64_t B,
                                                    int64_t C, int precision);
@@ -446,6 +449,20 @@ int wf_window_attention_fwd_levels(const float* const* x, const int64_t* dhw, in
                                    const float* bproj, float* out, void* workspace, int64_t B,
                                    int64_t C, int64_t heads, float scale, int precision,
                                    void* stream);
+/* wf_window_attention_fwd_levels with the source of q / k / v chosen by the caller (the tests):
+ * qkv_mode -1 = the rule above (what wf_window_attention_fwd_levels passes), 0 = the staged qkv
+ * GEMM, 1 = computed in the core; 1 at a width without a fused instantiation (other than
+ * C = 48 / 96) is WF_E_SHAPE.  The outputs of the three are bitwise equal.                     */
+int wf_window_attention_fwd_levels_mode(const float* const* x, const int64_t* dhw, int nlev,
+                                        const uint16_t* wqkv_bf16x2, const float* bqkv,
+                                        const float* table, const uint16_t* wproj_bf16x2,
+                                        const float* bproj, float* out, void* workspace,
+                                        int64_t B, int64_t C, int64_t heads, float scale,
+                                        int precision, void* stream, int qkv_mode);
+/* 1 if the rule computes q / k / v in the core for this level list, else 0 (also for an invalid
+ * list).  Host only.                                                                          */
+int wf_window_attention_levels_fused(const int64_t* dhw, int nlev, int64_t B, int64_t C,
+                                     int64_t heads, int precision);
 
 /* ---- a6: multi-scale fuse ------------------------------------------------------------- */
 /* Replaces the F.interpolate(trilinear, align_corners=False) + sum + shortcut of

@@ -93,6 +93,9 @@ SIGNATURES = {
     "wf_window_attention_levels_workspace_bytes": (_I64, [_P, _I, _I64, _I64, _I]),
     "wf_window_attention_fwd_levels": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I64, _I64,
                                             _I64, _F, _I, _P]),
+    "wf_window_attention_fwd_levels_mode": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I64,
+                                                 _I64, _I64, _F, _I, _P, _I]),
+    "wf_window_attention_levels_fused": (_I, [_P, _I, _I64, _I64, _I64, _I]),
     "wf_msfuse_fwd": (_I, [_P, _P, _I, _P, _P, _P, _P, _F, _I64, _I64, _I64, _I64, _I64, _P]),
     "wf_ccf_ffn_workspace_bytes": (_I64, [_I64, _I64, _I64, _I64, _I64, _I64, _I]),
     "wf_ccf_ffn_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _F, _P, _P,
@@ -141,7 +144,7 @@ SIGNATURES = {
     "wf_transpose_cs": (_I, [_P, _P, _I64, _I64, _I64, _P]),
 }
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 _lock = threading.Lock()
 _lib = None
 _err = None

@@ -4,7 +4,9 @@
 // Block.multi_scale_forward (wave_helper.py:482-499): window_partition -> qkv -> q*scale ->
 // q@k^T + relative_position_bias -> softmax -> @v -> proj, then the window "reverse" that is
 // a plain reshape (quirk Q1).  Here:
-//   qkv  : gemm_ares with the window gather (and norm1 for level-0 blocks) in its loader
+//   qkv  : gemm_ares with the window gather (and norm1 for level-0 blocks) in its loader; or no
+//          launch at all: the table-bias core computes q / k / v itself from x and the weight
+//          where attn_qkv_fused says so (attn_tbl_kernel_fused)
 //   core : one workgroup = (window b_, head h, 64 queries); flash-style loop over key tiles
 //          staged in LDS.  S^T = K.Q^T is computed "swapped" (keys on the MFMA rows, queries
 //          on the lanes) so the fp32 accumulator of S^T is, register for register, the B
@@ -15,7 +17,7 @@
 //   proj : gemm_ares; rows stay in window-major order, which is exactly the reference's
 //          reshaped raster (Q1).
 #include "attn_levels.hpp"
-#include "kernels.hpp"
+#include "gemm_common.hpp"
 
 namespace wf {
 
@@ -298,6 +300,198 @@ constexpr int TQ_BYTES = TBLN * 16;
 constexpr float kTau = 16.0f;
 }  // namespace tbl
 
+// ---- q / k / v computed in the core (attn_tbl_kernel_fused) -----------------------------------
+// The fused form takes x and the qkv weight instead of a staged (rows, 3 C) tensor: g is the qkv
+// GEMM's own argument block (MAP_LEVELS rows, K = C = CW, N = 3 C, the [2][3C][C] weight planes,
+// the bias), and every value is formed exactly as gemm_rows / gemm_kc form it -- the weight rows
+// as the MFMA's A operand, the activation octets through a_fragment as B, 32-deep k steps in
+// ascending order through mma3, the tail of K = 48 as gemm_kc's (load clamped at K - 8, the
+// activation octet zeroed), the bias added after the last step -- and then rounded as the staged
+// store + load8_split pair rounds it (split4: op_cvt / op_lo; bf16 storage is op_cvt itself).
+// So the two forms are bitwise equal and a launch may take either (attn_qkv_fused).
+template <int CW>
+struct FusedQkv {
+  static constexpr int NKS = (CW + 31) / 32;
+};
+
+// one 16 x 16 tile: 16 weight rows (fragments wh / wl: row l15) against 16 x rows (octets v:
+// row l15).  The lane ends with x row l15 against weight rows 4 g4 .. + 3, as the GEMMs' lanes do
+template <int P, int CW>
+__device__ __forceinline__ f32x4 fused_tile(const float (&v)[FusedQkv<CW>::NKS][8],
+                                            const bf16x8 (&wh)[FusedQkv<CW>::NKS],
+                                            const bf16x8 (&wl)[FusedQkv<CW>::NKS], int g4) {
+  f32x4 acc = f32x4{0, 0, 0, 0};
+#pragma unroll
+  for (int ks = 0; ks < FusedQkv<CW>::NKS; ++ks) {
+    const int k = ks * 32 + 8 * g4;
+    float x[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x[j] = v[ks][j];
+    bf16x8 ah, al;
+    a_fragment<P>(x, 0.f, 1.f, nullptr, nullptr, k, k < CW, false, false, ah, al);
+    acc = mma3<P>(acc, wh[ks], wl[ks], ah, al);
+  }
+  return acc;
+}
+template <int P, int CW>
+__device__ __forceinline__ void fused_load_w(const GemmArgs& g, int wo, int g4,
+                                             bf16x8 (&wh)[FusedQkv<CW>::NKS],
+                                             bf16x8 (&wl)[FusedQkv<CW>::NKS]) {
+#pragma unroll
+  for (int ks = 0; ks < FusedQkv<CW>::NKS; ++ks) {
+    const int off = wo + min(ks * 32 + 8 * g4, CW - 8);  // past K: a finite re-read x a zeroed octet
+    wh[ks] = *reinterpret_cast<const bf16x8*>(g.w + off);
+    wl[ks] = P == PREC_SPLIT ? *reinterpret_cast<const bf16x8*>(g.w + 3 * CW * CW + off) : wh[ks];
+  }
+}
+// The x rows of one window: RowMapper<MAP_LEVELS>'s map (gemm_common.hpp) with what a workgroup's
+// 512 rows share taken once -- they are one window of one level, so the level's raster and the
+// window's corner are wave-uniform (scalar registers, three divisions per workgroup) and a row is
+// the corner plus its token's (z, y, x) offset.  Through RowMapper itself every 16-row tile paid a
+// per-lane fetch of the level's geometry and the divisions in front of its loads.
+struct WindowRows {
+  const float* corner;  // channel 0 of the window's token 0
+  int H, W;             // the level's raster
+  __device__ __forceinline__ WindowRows() : corner(nullptr), H(0), W(0) {}
+  __device__ __forceinline__ WindowRows(const GemmArgs& g, int row0) {
+    row0 = __builtin_amdgcn_readfirstlane(row0);
+    const int l = (row0 >= g.lv_row0[1]) + (row0 >= g.lv_row0[2]) + (row0 >= g.lv_row0[3]);
+    const int r0 = l == 0 ? g.lv_row0[0] : l == 1 ? g.lv_row0[1] : l == 2 ? g.lv_row0[2] : g.lv_row0[3];
+    const int mD = l == 0 ? g.lv_D[0] : l == 1 ? g.lv_D[1] : l == 2 ? g.lv_D[2] : g.lv_D[3];
+    const int mH = l == 0 ? g.lv_H[0] : l == 1 ? g.lv_H[1] : l == 2 ? g.lv_H[2] : g.lv_H[3];
+    const int mW = l == 0 ? g.lv_W[0] : l == 1 ? g.lv_W[1] : l == 2 ? g.lv_W[2] : g.lv_W[3];
+    const float* src = l == 0 ? g.lv_src[0] : l == 1 ? g.lv_src[1] : l == 2 ? g.lv_src[2] : g.lv_src[3];
+    H = mH;
+    W = mW;
+    corner = src + (int64_t)window_row_pos(row0 - r0, 8, mD, mH, mW) * g.K;
+  }
+  // element offset of token t's row from the corner
+  __device__ __forceinline__ int64_t row(int t, int K) const {
+    return (int64_t)(((t >> 6) * H + ((t >> 3) & 7)) * W + (t & 7)) * K;
+  }
+};
+template <int CW>
+__device__ __forceinline__ void fused_load_x(const WindowRows& w, int t, int g4,
+                                             float (&v)[FusedQkv<CW>::NKS][8]) {
+  const int64_t off = w.row(t, CW);
+#pragma unroll
+  for (int ks = 0; ks < FusedQkv<CW>::NKS; ++ks)
+    load8f<false>(w.corner, off + min(ks * 32 + 8 * g4, CW - 8), v[ks]);
+}
+
+// K and V of the window's 512 rows into Ks / Vq (their staged layouts): wave wid takes rows
+// 64 wid .. + 63 as four 16-row tiles against this head's 16 K and 16 V weight rows.  One pass
+// with both weight sets at C = 48; at C = 96 they and the rows in flight do not fit the 128
+// registers of four waves per SIMD together, so K and V are a pass each (the second pass reads
+// the rows again, from L2).
+template <int P, int CW, bool DOK, bool DOV>
+__device__ __forceinline__ void fused_stage_pass(const GemmArgs& g, const WindowRows& w, int h,
+                                                 uint16_t* Ks, uint16_t* Vq) {
+  using namespace tbl;
+  constexpr int NKS = FusedQkv<CW>::NKS;
+  constexpr bool SPLIT = P == PREC_SPLIT;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int l15 = lane & 15, g4 = lane >> 4;
+  bf16x8 kwh[NKS], kwl[NKS], vwh[NKS], vwl[NKS];
+  if (DOK) fused_load_w<P, CW>(g, (CW + h * HD + l15) * CW, g4, kwh, kwl);
+  if (DOV) fused_load_w<P, CW>(g, (2 * CW + h * HD + l15) * CW, g4, vwh, vwl);
+  f32x4 kb = f32x4{0, 0, 0, 0}, vb = kb;
+  if (g.bias) {
+    if (DOK) kb = *reinterpret_cast<const f32x4*>(g.bias + CW + h * HD + 4 * g4);
+    if (DOV) vb = *reinterpret_cast<const f32x4*>(g.bias + 2 * CW + h * HD + 4 * g4);
+  }
+  // DEPTH tiles' rows in flight: all four at C = 48 (64 registers), two at C = 96
+  constexpr int DEPTH = CW <= 48 ? 4 : 2;
+  float v[DEPTH][NKS][8];
+#pragma unroll
+  for (int tt = 0; tt < DEPTH; ++tt) fused_load_x<CW>(w, wid * 64 + tt * 16 + l15, g4, v[tt]);
+#pragma unroll
+  for (int tt = 0; tt < 4; ++tt) {
+    const int key = wid * 64 + tt * 16 + l15;
+    f32x4 ka = f32x4{0, 0, 0, 0}, va = ka;
+    if (DOK) ka = fused_tile<P, CW>(v[tt % DEPTH], kwh, kwl, g4);
+    if (DOV) va = fused_tile<P, CW>(v[tt % DEPTH], vwh, vwl, g4);
+    if (tt + DEPTH < 4) fused_load_x<CW>(w, key + 16 * DEPTH, g4, v[tt % DEPTH]);
+    if (g.bias) {
+      ka += kb;
+      va += vb;
+    }
+    if (DOK) {
+      bf16x4 kh, kl;
+      split4<P>(ka, kh, kl);
+      const int sw = kswz(key), hc = g4 >> 1, ho = 4 * (g4 & 1);
+      *reinterpret_cast<bf16x4*>(&Ks[key * KS + 8 * (hc ^ sw) + ho]) = kh;
+      *reinterpret_cast<bf16x4*>(&Ks[key * KS + 8 * ((2 + hc) ^ sw) + ho]) =
+          SPLIT ? kl : bf16x4{0, 0, 0, 0};
+    }
+    if (DOV) {
+      bf16x4 vh, vl;
+      split4<P>(va, vh, vl);
+      const int vo = (key >> 2) * VB + (4 * g4) * 4 + (key & 3);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        Vq[vo + 4 * i] = (uint16_t)vh[i];
+        if (SPLIT) Vq[VQ + vo + 4 * i] = (uint16_t)vl[i];
+      }
+    }
+  }
+}
+template <int P, int CW>
+__device__ __forceinline__ void fused_stage_kv(const GemmArgs& g, int row0, int h, uint16_t* Ks,
+                                               uint16_t* Vq) {
+  const WindowRows w(g, row0);
+  if constexpr (CW <= 48) {
+    fused_stage_pass<P, CW, true, true>(g, w, h, Ks, Vq);
+  } else {
+    fused_stage_pass<P, CW, true, false>(g, w, h, Ks, Vq);
+    fused_stage_pass<P, CW, false, true>(g, w, h, Ks, Vq);
+  }
+}
+
+// The S operands of 16 queries (lane: token t of the window w): Q' = Q * sc rounded as
+// load8_split_scaled rounds the staged Q, then moved from the accumulator layout (channels
+// 4 g4 .. + 3) to the operand slots (8 values 8 (g4 & 1) .. + 7: two lanes' quads)
+template <int P, int CW>
+__device__ __forceinline__ void fused_q_operands(const GemmArgs& g, const WindowRows& w, int t,
+                                                 int h, float sc, bf16x8& hi, bf16x8& lo) {
+  using namespace tbl;
+  constexpr int NKS = FusedQkv<CW>::NKS;
+  const int lane = threadIdx.x & 63, l15 = lane & 15, g4 = lane >> 4;
+  // the weight fragments are loaded per sub-tile (L2 hits): held across the tile loop they would
+  // not fit its registers, so the loads hang on a value the compiler cannot hoist
+  int wo = (h * HD + l15) * CW;
+  asm volatile("" : "+v"(wo));
+  bf16x8 wh[NKS], wl[NKS];
+  fused_load_w<P, CW>(g, wo, g4, wh, wl);
+  float v[NKS][8];
+  fused_load_x<CW>(w, t, g4, v);
+  f32x4 q = fused_tile<P, CW>(v, wh, wl, g4);
+  if (g.bias) q += *reinterpret_cast<const f32x4*>(g.bias + h * HD + 4 * g4);
+  bf16x4 qh, ql;
+  if (store32(P)) {
+    // load8_split_scaled's text: with FMA contraction the lo part is bf16(fma(q, sc, -hi)), the
+    // product unrounded, and only the same expression gives the same bits
+    const f32x4 a = q * sc;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const uint16_t hh = op_cvt<P>(a[i]);
+      qh[i] = (short)hh;
+      ql[i] = op_lo<P>(a[i], hh);
+    }
+  } else {  // bf16 storage of the staged Q, then the scale
+#pragma unroll
+    for (int i = 0; i < 4; ++i) qh[i] = (short)f2bf(bf2f(f2bf(q[i])) * sc);
+    ql = bf16x4{0, 0, 0, 0};
+  }
+  const u32x2 hw = __builtin_bit_cast(u32x2, qh), lw = __builtin_bit_cast(u32x2, ql);
+  const int sa = l15 + 32 * (g4 & 1), sb = sa + 16;
+  hi = __builtin_bit_cast(bf16x8, u32x4{(uint32_t)__shfl((int)hw[0], sa, 64), (uint32_t)__shfl((int)hw[1], sa, 64),
+                                        (uint32_t)__shfl((int)hw[0], sb, 64), (uint32_t)__shfl((int)hw[1], sb, 64)});
+  if (P == PREC_SPLIT)
+    lo = __builtin_bit_cast(bf16x8, u32x4{(uint32_t)__shfl((int)lw[0], sa, 64), (uint32_t)__shfl((int)lw[1], sa, 64),
+                                          (uint32_t)__shfl((int)lw[0], sb, 64), (uint32_t)__shfl((int)lw[1], sb, 64)});
+}
+
 // The tile loop of attn_tbl_kernel over this wave's 16-query sub-tiles, NQ at a time (sub-tiles
 // st, st + 8, ...; q0 = the workgroup's first query).  NQ = 2: every K / V fragment read from
 // LDS feeds both sub-tiles, and their dependency chains (scores -> max -> exp -> PV)
@@ -319,8 +513,11 @@ constexpr float kTau = 16.0f;
 //    must not depend on the batch (the qsplit = 4 launches of small grids run NQ = 1);
 //  * the split's lo part of a pair of probabilities comes from split_pair (v_dot2c_f32_bf16
 //    against the packed hi pair), bitwise the unpack-and-subtract form.
-template <int P, int NQ>
-__device__ __forceinline__ void attn_tbl_tiles(const void* __restrict__ qkv, void* __restrict__ out,
+// CW != 0: the fused form -- Q' of a sub-tile comes from x and the weight (g; fused_q_operands)
+// where the staged form reads it from qkv.
+template <int P, int NQ, int CW = 0>
+__device__ __forceinline__ void attn_tbl_tiles(const void* __restrict__ qkv,
+                                               const GemmArgs* __restrict__ g, void* __restrict__ out,
                                                const f32x4* tq, const uint16_t* Ks,
                                                const uint16_t* Vq, int64_t row0, int q0, int h,
                                                int heads, int nsub, float scale_log2) {
@@ -334,6 +531,8 @@ __device__ __forceinline__ void attn_tbl_tiles(const void* __restrict__ qkv, voi
   const bf16x8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
   const short one = (short)op_cvt<P>(1.0f);
   const bf16x8 ones = bf16x8{one, one, one, one, one, one, one, one};
+  // fused: the window's x rows (scalars; the staged form never reads g)
+  const WindowRows wrows = CW != 0 ? WindowRows(*g, (int)row0) : WindowRows();
   for (int st = wid; st < nsub; st += 8 * NQ) {
     int qq[NQ], rbq[NQ];
     bf16x8 b1[NQ], b2[NQ];
@@ -345,7 +544,10 @@ __device__ __forceinline__ void attn_tbl_tiles(const void* __restrict__ qkv, voi
       qq[u] = q;
       // B operands of S: slots 8 g4 .. +7 <- Q'[q][8 (g4 & 1) ..]: [Q'h | Q'h] and [Q'l | 0]
       bf16x8 hi = z8, lo = z8;
-      load8_split_scaled<P>(qkv, (row0 + q) * ld + h * HD + 8 * (g4 & 1), scale_log2, hi, lo);
+      if constexpr (CW != 0)
+        fused_q_operands<P, CW>(*g, wrows, q, h, scale_log2, hi, lo);
+      else
+        load8_split_scaled<P>(qkv, (row0 + q) * ld + h * HD + 8 * (g4 & 1), scale_log2, hi, lo);
       b1[u] = hi;
       b2[u] = (SPLIT && g4 < 2) ? lo : z8;
       const int qz = q >> 6, qy = (q >> 3) & 7, qx = q & 7;
@@ -454,6 +656,22 @@ __device__ __forceinline__ void attn_tbl_tiles(const void* __restrict__ qkv, voi
   }
 }
 
+// head h's column of the table, log2 e-scaled, as the reversed overlapping quads (tbl::TQ_BYTES)
+__device__ __forceinline__ void attn_tbl_stage_table(f32x4* tq, const float* __restrict__ table,
+                                                     int heads, int h) {
+  using namespace tbl;
+  for (int i = threadIdx.x; i < TBLN; i += 512) {
+    // tq[j].c = tbr[j + c] = table[TBLN - 1 - j - c] (0 past the end: never read)
+    const float v = table[(int64_t)i * heads + h] * 1.4426950408889634f;
+    const int j = TBLN - 1 - i;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (j - c >= 0) reinterpret_cast<float*>(&tq[j - c])[c] = v;
+    if (j >= TBLN - 3)
+      for (int c = TBLN - j; c < 4; ++c) reinterpret_cast<float*>(&tq[j])[c] = 0.f;
+  }
+}
+
 template <int P>
 __global__ __launch_bounds__(512, 2) void attn_tbl_kernel(const void* __restrict__ qkv,
                                                           const float* __restrict__ table,
@@ -481,16 +699,7 @@ __global__ __launch_bounds__(512, 2) void attn_tbl_kernel(const void* __restrict
   const int64_t row0 = bw * N;
   const bf16x8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
 
-  for (int i = tid; i < TBLN; i += 512) {
-    // tq[j].c = tbr[j + c] = table[TBLN - 1 - j - c] (0 past the end: never read)
-    const float v = table[(int64_t)i * heads + h] * 1.4426950408889634f;
-    const int j = TBLN - 1 - i;
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-      if (j - c >= 0) reinterpret_cast<float*>(&tq[j - c])[c] = v;
-    if (j >= TBLN - 3)
-      for (int c = TBLN - j; c < 4; ++c) reinterpret_cast<float*>(&tq[j])[c] = 0.f;
-  }
+  attn_tbl_stage_table(tq, table, heads, h);
   for (int it = tid; it < N * 2; it += 512) {  // K: (key, 8-value chunk)
     const int key = it >> 1, ch = it & 1, sw = kswz(key);
     bf16x8 hi = z8, lo = z8;
@@ -519,16 +728,49 @@ __global__ __launch_bounds__(512, 2) void attn_tbl_kernel(const void* __restrict
   const int nsub = N / 16 / qsplit;  // 16-query sub-tiles of this workgroup
   const int q0 = qs * (N / qsplit);
   if (nsub >= 16 && bw < pair_end)
-    attn_tbl_tiles<P, 2>(qkv, out, tq, Ks, Vq, row0, q0, h, heads, nsub, scale_log2);
+    attn_tbl_tiles<P, 2>(qkv, nullptr, out, tq, Ks, Vq, row0, q0, h, heads, nsub, scale_log2);
   else
-    attn_tbl_tiles<P, 1>(qkv, out, tq, Ks, Vq, row0, q0, h, heads, nsub, scale_log2);
+    attn_tbl_tiles<P, 1>(qkv, nullptr, out, tq, Ks, Vq, row0, q0, h, heads, nsub, scale_log2);
 }
 
-bool attn_tbl_pair_loop(int64_t wh) { return wh >= 256; }
+// attn_tbl_kernel with q / k / v computed here from x and the qkv weight (g: the qkv GEMM's
+// arguments, MAP_LEVELS rows of width CW) instead of read from a tensor the GEMM stored: the
+// prologue fills Ks / Vq through fused_stage_kv, the tile loop forms each sub-tile's Q' itself.
+// With qsplit > 1 every workgroup of a (window, head) projects all 512 K / V rows again, so the
+// host takes this form at qsplit <= 2 only (attn_qkv_fused).  Same LDS block, same tile loops,
+// bitwise the staged kernel's output.
+template <int P, int CW>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void attn_tbl_kernel_fused(const GemmArgs g,
+                                                                const float* __restrict__ table,
+                                                                void* __restrict__ out, int heads,
+                                                                int qsplit, float scale_log2,
+                                                                int64_t pair_end) {
+  using namespace tbl;
+  __shared__ __attribute__((aligned(16))) uint8_t lds_tbl[TQ_BYTES + N * KS * 2 + 2 * VQ * 2];
+  f32x4* tq = reinterpret_cast<f32x4*>(lds_tbl);
+  uint16_t* Ks = reinterpret_cast<uint16_t*>(lds_tbl + TQ_BYTES);
+  uint16_t* Vq = Ks + N * KS;
+  int qs, h;
+  int64_t bw;
+  attn_block(qsplit, heads, qs, h, bw);
+  const int64_t row0 = bw * N;
+  attn_tbl_stage_table(tq, table, heads, h);
+  fused_stage_kv<P, CW>(g, (int)row0, h, Ks, Vq);
+  __syncthreads();
+
+  const int nsub = N / 16 / qsplit;  // 16-query sub-tiles of this workgroup
+  const int q0 = qs * (N / qsplit);
+  if (nsub >= 16 && bw < pair_end)
+    attn_tbl_tiles<P, 2, CW>(nullptr, &g, out, tq, Ks, Vq, row0, q0, h, heads, nsub, scale_log2);
+  else
+    attn_tbl_tiles<P, 1, CW>(nullptr, &g, out, tq, Ks, Vq, row0, q0, h, heads, nsub, scale_log2);
+}
+
+bool attn_tbl_pair_loop(int64_t wh) { return wh >= kAttnPairLoopWH; }
 
 int launch_attn_core(const void* qkv, const float* bias, void* out, float* lse, int64_t Bw,
                      int N, int heads, int hd, float scale, int prec, hipStream_t s,
-                     int table_ws, int64_t pair_windows) {
+                     int table_ws, int64_t pair_windows, const GemmArgs* fused) {
   if (Bw <= 0) return WF_OK;
   const int64_t nblk = cdiv(N, kQB) * heads * Bw;
   if (nblk > 0x7fffffff) return fail(WF_E_SHAPE, "attention: too many (window, head) tiles");
@@ -549,6 +791,20 @@ int launch_attn_core(const void* qkv, const float* bias, void* out, float* lse, 
     auto k = split ? attn_tbl_kernel<PREC_SPLIT>
                    : (f16 ? attn_tbl_kernel<PREC_FP16> : attn_tbl_kernel<PREC_BF16>);
     const int64_t pair_end = pair_windows < 0 ? Bw : pair_windows;
+    if (fused) {  // q / k / v from x and the weight: *fused is the qkv GEMM's argument block
+      void (*kf)(GemmArgs, const float*, void*, int, int, float, int64_t) = nullptr;
+#define ATTN_FUSED_CASE(CWV)                                                               \
+  if (fused->K == CWV)                                                                     \
+    kf = split ? attn_tbl_kernel_fused<PREC_SPLIT, CWV>                                    \
+               : (f16 ? attn_tbl_kernel_fused<PREC_FP16, CWV> : attn_tbl_kernel_fused<PREC_BF16, CWV>);
+      ATTN_FUSED_CASE(48)
+      ATTN_FUSED_CASE(96)
+#undef ATTN_FUSED_CASE
+      if (!kf || !gemm_levels_callsite(*fused) || fused->N != 3 * fused->K || heads * 16 != fused->K)
+        return fail(WF_E_SHAPE, "attention core (q/k/v in the core): instantiated for C = 48 and 96");
+      hipLaunchKernelGGL(kf, g1, dim3(512), 0, s, *fused, bias, out, heads, qsplit, sl2, pair_end);
+      return check_launch("attention core (table bias, q/k/v in the core)");
+    }
     hipLaunchKernelGGL(k, g1, dim3(512), 0, s, qkv, bias, out, heads, qsplit, sl2, pair_end);
     return check_launch("attention core (table bias, window per workgroup)");
   }
@@ -628,6 +884,31 @@ static GemmArgs qkv_gemm_args(const float* x, const float* ln_w, const float* ln
   return g;
 }
 
+// the rows of g come from the levels of L (MAP_LEVELS)
+static void set_level_sources(GemmArgs& g, const float* const* x, const AttnLevels& L) {
+  g.a_map = MAP_LEVELS;
+  for (int l = 0; l < WF_MAX_LEVELS; ++l) {
+    const bool on = l < L.nlev;
+    g.lv_src[l] = on ? x[l] : x[0];
+    g.lv_row0[l] = on ? (int)L.row0[l] : 0x7fffffff;
+    g.lv_D[l] = on ? L.D[l] : kAttnLevelsWs;
+    g.lv_H[l] = on ? L.H[l] : kAttnLevelsWs;
+    g.lv_W[l] = on ? L.W[l] : kAttnLevelsWs;
+  }
+}
+
+// whether a table-bias launch over `windows` windows computes q / k / v in the core; 0 / 1, or
+// < 0 with the error set when the fused form is asked for at a width it is not instantiated for
+static int pick_qkv_fused(int qkv_mode, int64_t windows, int64_t heads, int64_t C) {
+  if (qkv_mode == ATTN_QKV_STAGED) return 0;
+  if (qkv_mode == ATTN_QKV_FUSED) {
+    if (!attn_qkv_fused_width(C))
+      return fail(WF_E_SHAPE, "window attention: q/k/v in the core is instantiated for C = 48 and 96");
+    return 1;
+  }
+  return attn_qkv_fused(windows, heads, C) ? 1 : 0;
+}
+
 // out = Linear(core output); window-major rows == the reshaped raster (Q1)
 static GemmArgs proj_gemm_args(const void* ao, const uint16_t* wproj, const float* bproj,
                                float* out, int64_t rows, int64_t C, int prec) {
@@ -678,7 +959,8 @@ static int window_attention_impl(const float* x, const float* ln_w, const float*
                                  const uint16_t* wproj_bf16x2, const float* bproj, float* out,
                                  void* workspace, float* lse, int64_t B, int64_t C, int64_t D1,
                                  int64_t H1, int64_t W1, int64_t ws, int64_t heads, float scale,
-                                 int precision, void* stream) {
+                                 int precision, void* stream,
+                                 int qkv_mode = ATTN_QKV_STAGED) {
   WF_REQUIRE(B >= 1 && C >= 8 && C % 8 == 0, "C must be a positive multiple of 8");
   WF_REQUIRE(ws >= 1 && D1 % ws == 0 && H1 % ws == 0 && W1 % ws == 0,
              "the raster must tile into ws^3 windows (window_partition, wave_helper.py:459)");
@@ -697,6 +979,30 @@ static int window_attention_impl(const float* x, const float* ln_w, const float*
   hipStream_t s = (hipStream_t)stream;
   void* qkv = workspace;
   void* ao = reinterpret_cast<char*>(workspace) + attn_workspace(rows, C, precision).ao;
+  // the table-bias core without a LayerNorm in the loader may compute q / k / v itself: the
+  // raster as the one level of a MAP_LEVELS argument block (same rows as MAP_WINDOW's)
+  if (table_ws == kAttnLevelsWs && !ln_w && !lse && C == 16 * heads && rows <= 0x7fffffff &&
+      reinterpret_cast<uintptr_t>(x) % 16 == 0) {
+    const int fused = pick_qkv_fused(qkv_mode, Bw, heads, C);
+    if (fused < 0) return WF_E_SHAPE;
+    if (fused) {
+      const int64_t dhw[3] = {D1, H1, W1};
+      AttnLevels L;
+      if (const char* why = attn_levels_plan(dhw, 1, B, C, heads, L))
+        return fail(WF_E_SHAPE, std::string("window attention: ") + why);
+      GemmArgs g = qkv_gemm_args(x, nullptr, nullptr, 0.f, wqkv_bf16x2, bqkv, qkv, rows, B, C, 0, 0,
+                                 0, ws, precision);
+      set_level_sources(g, &x, L);
+      const int rc = launch_attn_core(nullptr, bias, ao, nullptr, Bw, (int)N, (int)heads, 16, scale,
+                                      precision, s, table_ws, -1, &g);
+      if (rc) return rc;
+      return launch_gemm(proj_gemm_args(ao, wproj_bf16x2, bproj, out, rows, C, precision), s,
+                         "wf_window_attention_fwd(proj)");
+    }
+  } else if (qkv_mode == ATTN_QKV_FUSED) {
+    return fail(WF_E_SHAPE, "window attention: q/k/v in the core needs the table bias (ws 8, "
+                            "head_dim 16), inference, no LayerNorm in the loader");
+  }
   // 1. qkv = Linear(window_partition(norm1?(x)))
   int rc = launch_gemm(qkv_gemm_args(x, ln_w, ln_b, ln_eps, wqkv_bf16x2, bqkv, qkv, rows, B, C,
                                      D1, H1, W1, ws, precision),
@@ -736,7 +1042,7 @@ extern "C" int wf_window_attention_fwd_table(const float* x, const float* ln_w,
              "table-bias attention is implemented for window 8 and head_dim 16");
   return window_attention_impl(x, ln_w, ln_b, ln_eps, wqkv_bf16x2, bqkv, table, (int)ws,
                                wproj_bf16x2, bproj, out, workspace, nullptr, B, C, D1, H1, W1,
-                               ws, heads, scale, precision, stream);
+                               ws, heads, scale, precision, stream, ATTN_QKV_RULE);
 }
 
 extern "C" int wf_window_attention_fwd(const float* x, const float* ln_w, const float* ln_b,
@@ -758,6 +1064,9 @@ extern "C" int wf_window_attention_fwd(const float* x, const float* ln_w, const 
 // row's arithmetic is what the per-level call does, so the outputs are bitwise equal: a GEMM row
 // does not depend on the rows it shares a launch with, and the core's result depends on its grid
 // only through which of its two loops a window takes, which the merged launch keeps per level.
+// Where the rule says so (attn_qkv_fused: C = 48 and 256 or more (window, head)s) there is no qkv
+// GEMM launch at all: the core computes q / k / v from the level rasters and the weight, bitwise
+// the GEMM's values, and the qkv part of the workspace is left untouched.
 extern "C" int64_t wf_window_attention_levels_workspace_bytes(const int64_t* dhw, int nlev,
                                                               int64_t B, int64_t C,
                                                               int precision) {
@@ -766,12 +1075,33 @@ extern "C" int64_t wf_window_attention_levels_workspace_bytes(const int64_t* dhw
   return attn_workspace(L.row0[nlev], C, precision).bytes;
 }
 
+extern "C" int wf_window_attention_levels_fused(const int64_t* dhw, int nlev, int64_t B, int64_t C,
+                                               int64_t heads, int precision) {
+  AttnLevels L;
+  if (!valid_prec(precision) || attn_levels_plan(dhw, nlev, B, C, heads, L)) return 0;
+  return attn_qkv_fused(L.row0[nlev] / (kAttnLevelsWs * kAttnLevelsWs * kAttnLevelsWs), heads, C) ? 1 : 0;
+}
+
 extern "C" int wf_window_attention_fwd_levels(const float* const* x, const int64_t* dhw, int nlev,
                                               const uint16_t* wqkv_bf16x2, const float* bqkv,
                                               const float* table, const uint16_t* wproj_bf16x2,
                                               const float* bproj, float* out, void* workspace,
                                               int64_t B, int64_t C, int64_t heads, float scale,
                                               int precision, void* stream) {
+  return wf_window_attention_fwd_levels_mode(x, dhw, nlev, wqkv_bf16x2, bqkv, table, wproj_bf16x2,
+                                             bproj, out, workspace, B, C, heads, scale, precision,
+                                             stream, ATTN_QKV_RULE);
+}
+
+extern "C" int wf_window_attention_fwd_levels_mode(const float* const* x, const int64_t* dhw,
+                                                   int nlev, const uint16_t* wqkv_bf16x2,
+                                                   const float* bqkv, const float* table,
+                                                   const uint16_t* wproj_bf16x2,
+                                                   const float* bproj, float* out, void* workspace,
+                                                   int64_t B, int64_t C, int64_t heads, float scale,
+                                                   int precision, void* stream, int qkv_mode) {
+  WF_REQUIRE(qkv_mode >= ATTN_QKV_RULE && qkv_mode <= ATTN_QKV_FUSED,
+             "qkv_mode: -1 (the rule), 0 (staged) or 1 (q/k/v in the core)");
   AttnLevels L;
   if (const char* why = attn_levels_plan(dhw, nlev, B, C, heads, L))
     return fail(WF_E_SHAPE, std::string(__func__) + ": " + why);
@@ -791,18 +1121,13 @@ extern "C" int wf_window_attention_fwd_levels(const float* const* x, const int64
   hipStream_t s = (hipStream_t)stream;
   void* qkv = workspace;
   void* ao = reinterpret_cast<char*>(workspace) + attn_workspace(rows, C, precision).ao;
-  // 1. qkv = Linear(window_partition(x_l)) of every level: the rows' sources come from lv_*
+  const int fused = pick_qkv_fused(qkv_mode, rows / N, heads, C);
+  if (fused < 0) return WF_E_SHAPE;
+  // 1. qkv = Linear(window_partition(x_l)) of every level: the rows' sources come from lv_*.
+  //    A launch of its own (staged), or the argument block the core computes q / k / v from
   GemmArgs g = qkv_gemm_args(x[0], nullptr, nullptr, 0.f, wqkv_bf16x2, bqkv, qkv, rows, B, C, 0,
                              0, 0, ws, precision);
-  g.a_map = MAP_LEVELS;
-  for (int l = 0; l < WF_MAX_LEVELS; ++l) {
-    const bool on = l < nlev;
-    g.lv_src[l] = on ? x[l] : x[0];
-    g.lv_row0[l] = on ? (int)L.row0[l] : 0x7fffffff;
-    g.lv_D[l] = on ? L.D[l] : (int)ws;
-    g.lv_H[l] = on ? L.H[l] : (int)ws;
-    g.lv_W[l] = on ? L.W[l] : (int)ws;
-  }
+  set_level_sources(g, x, L);
   // the core loop each level's own launch takes (attn_tbl_kernel, pair_end): the merged launch
   // keeps it per level, so the levels on the query-pair loop must come first
   int64_t pair_windows = 0;
@@ -814,23 +1139,23 @@ extern "C" int wf_window_attention_fwd_levels(const float* const* x, const int64
       pair_windows = L.row0[l + 1] / N;
     }
   }
-  if (!prefix || (!try_launch_gemm_rows(g, s, true) && !try_launch_gemm_kc(g, s))) {
+  if (!prefix || (!fused && !try_launch_gemm_rows(g, s, true) && !try_launch_gemm_kc(g, s))) {
     // no multi-level instantiation takes this width (or a coarse level before a finer one):
     // one call per level, into the same output
     for (int l = 0; l < nlev; ++l) {
       const int rc = window_attention_impl(x[l], nullptr, nullptr, 0.f, wqkv_bf16x2, bqkv, table,
                                            (int)ws, wproj_bf16x2, bproj, out + L.row0[l] * C,
                                            workspace, nullptr, B, C, L.D[l], L.H[l], L.W[l], ws,
-                                           heads, scale, precision, stream);
+                                           heads, scale, precision, stream, qkv_mode);
       if (rc) return rc;
     }
     return WF_OK;
   }
-  int rc = check_launch("wf_window_attention_fwd_levels(qkv)");
+  int rc = fused ? WF_OK : check_launch("wf_window_attention_fwd_levels(qkv)");
   if (rc) return rc;
   // 2. softmax(q k^T * scale + bias) v over all levels' windows
   rc = launch_attn_core(qkv, table, ao, nullptr, rows / N, (int)N, (int)heads, 16, scale,
-                        precision, s, (int)ws, pair_windows);
+                        precision, s, (int)ws, pair_windows, fused ? &g : nullptr);
   if (rc) return rc;
   // 3. proj; window-major rows, level after level
   return launch_gemm(proj_gemm_args(ao, wproj_bf16x2, bproj, out, rows, C, precision), s,

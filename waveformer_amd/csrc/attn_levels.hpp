@@ -40,4 +40,26 @@ inline const char* attn_levels_plan(const int64_t* dhw, int nlev, int64_t B, int
   return nullptr;
 }
 
+// A core launch over wh (window, head)s takes the query-pair loop, and splits the queries of a
+// (window, head) over at most two workgroups, from this many on (attn_tbl_pair_loop).
+constexpr int64_t kAttnPairLoopWH = 256;
+
+// How a table-bias launch gets its q / k / v (the qkv_mode of wf_window_attention_fwd_levels_mode)
+enum AttnQkvMode { ATTN_QKV_RULE = -1, ATTN_QKV_STAGED = 0, ATTN_QKV_FUSED = 1 };
+
+// the widths the core computes q / k / v for itself (attn_tbl_kernel_fused's instantiations)
+inline bool attn_qkv_fused_width(int64_t C) { return C == 48 || C == 96; }
+
+// The rule: a table-bias inference launch over `windows` windows computes q / k / v in the core,
+// without the qkv GEMM launch and its (rows, 3 C) round trip, at C = 48 when the queries of a
+// (window, head) are split over at most two workgroups: each of them projects all of the window's
+// K / V rows, so at a split of four (small grids) the staged GEMM stays.  C = 96 stays staged as
+// well: its 6 heads x 2 query halves read every x row twelve times and the B = 8 stage-2 launch
+// measured 123 us fused against 101 us for GEMM + core; the instantiation is
+// there for qkv_mode 1.  The two forms are bitwise equal, so launches on either side of the rule
+// agree.
+inline bool attn_qkv_fused(int64_t windows, int64_t heads, int64_t C) {
+  return C == 48 && windows * heads >= kAttnPairLoopWH;
+}
+
 }  // namespace wf

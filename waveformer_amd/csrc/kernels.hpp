@@ -187,9 +187,11 @@ int try_launch_gemm_rows(const GemmArgs& g, hipStream_t s, bool single_chunk_onl
 // pair_windows (table bias, inference): windows [0, pair_windows) may take the core's
 // query-pair loop, the rest its one-sub-tile loop (< 0: all may); attn_tbl_pair_loop(wh) is the
 // loop a launch of wh (window, head)s takes on its own
+// fused (table bias, inference): the qkv GEMM's argument block (MAP_LEVELS rows); the core then
+// computes q / k / v itself from x and the weight and `qkv` is not read (attn_tbl_kernel_fused)
 int launch_attn_core(const void* qkv, const float* bias, void* out, float* lse, int64_t Bw,
                      int N, int heads, int hd, float scale, int prec, hipStream_t s,
-                     int table_ws = 0, int64_t pair_windows = -1);
+                     int table_ws = 0, int64_t pair_windows = -1, const GemmArgs* fused = nullptr);
 bool attn_tbl_pair_loop(int64_t wh);
 
 // ---- depthwise 3^3 conv + bias + LayerNorm + GELU over a channel-last volume ------------

@@ -1412,7 +1412,8 @@ def window_attention(x_cl: torch.Tensor, wqkv: torch.Tensor, bqkv: Optional[torc
                      bias: torch.Tensor, wproj: torch.Tensor, bproj: Optional[torch.Tensor],
                      ws: int, heads: int, scale: float,
                      ln: Optional[Tuple[torch.Tensor, torch.Tensor, float]] = None,
-                     prec: Optional[int] = None, more: Sequence[torch.Tensor] = ()):
+                     prec: Optional[int] = None, more: Sequence[torch.Tensor] = (),
+                     qkv_mode: int = -1):
     """window_partition + Attention.forward + reshape-reverse (Q1) over a channel-last raster.
     Returns (B, D1, H1, W1, C) whose rows are the window-major attention outputs.  `bias` is
     the dense (heads, N, N) bias, or the ((2ws-1)^3, heads) table itself when the index is the
@@ -1422,13 +1423,18 @@ def window_attention(x_cl: torch.Tensor, wqkv: torch.Tensor, bqkv: Optional[torc
     LL levels of a multi-scale Block.  All levels then run as one launch set
     (wf_window_attention_fwd_levels: table bias, no LayerNorm) and the result is a tuple of
     per-level views, x_cl's first, of one output buffer; each is bitwise what a call on that
-    level alone returns."""
+    level alone returns.
+
+    qkv_mode (tests; with `more` or as a one-level list, table bias without a LayerNorm): where
+    q / k / v come from -- -1 the library's rule, 0 the staged qkv GEMM, 1 computed in the core
+    (wf_window_attention_fwd_levels_mode).  The three are bitwise equal."""
     _check(x_cl, "x")
     B, D1, H1, W1, C = x_cl.shape
     prec = _prec() if prec is None else prec
-    if more:
-        return _window_attention_levels((x_cl, *more), wqkv, bqkv, bias, wproj, bproj, ws, heads,
-                                        scale, ln, prec)
+    if more or qkv_mode != -1:
+        out = _window_attention_levels((x_cl, *more), wqkv, bqkv, bias, wproj, bproj, ws, heads,
+                                       scale, ln, prec, qkv_mode)
+        return out if more else out[0]
     wq = split_weight(wqkv, prec=prec)
     wp = split_weight(wproj, prec=prec)
     if bqkv is not None:
@@ -1457,7 +1463,8 @@ def window_attention(x_cl: torch.Tensor, wqkv: torch.Tensor, bqkv: Optional[torc
     return out
 
 
-def _window_attention_levels(levels, wqkv, bqkv, bias, wproj, bproj, ws, heads, scale, ln, prec):
+def _window_attention_levels(levels, wqkv, bqkv, bias, wproj, bproj, ws, heads, scale, ln, prec,
+                             qkv_mode=-1):
     """window_attention(levels[0], ..., more=levels[1:])."""
     B, C = levels[0].shape[0], levels[0].shape[4]
     if ln is not None or ws != 8 or tuple(bias.shape) != ((2 * ws - 1) ** 3, heads):
@@ -1480,9 +1487,9 @@ def _window_attention_levels(levels, wqkv, bqkv, bias, wproj, bproj, ws, heads, 
     out = torch.empty((sum(rows), C), dtype=torch.float32, device=levels[0].device)
     work = torch.empty(max(wsb, 0), dtype=torch.uint8, device=out.device)
     arr = (ctypes.c_void_p * len(levels))(*[x.data_ptr() for x in levels])
-    _lib.call("wf_window_attention_fwd_levels", arr, darr, len(levels), wq.data_ptr(),
+    _lib.call("wf_window_attention_fwd_levels_mode", arr, darr, len(levels), wq.data_ptr(),
               _ptr(bqkv), bias.data_ptr(), wp.data_ptr(), _ptr(bproj), out.data_ptr(),
-              work.data_ptr(), B, C, heads, float(scale), prec, _stream())
+              work.data_ptr(), B, C, heads, float(scale), prec, _stream(), int(qkv_mode))
     views = LevelViews(o.view(x.shape) for o, x in zip(out.split(rows), levels))
     views.buffer = out
     return views
