@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define WF_ABI_VERSION 21
+#define WF_ABI_VERSION 22
 
 enum { WF_PREC_BF16 = 0, WF_PREC_BF16X3 = 1, WF_PREC_FP16 = 2 };
 
@@ -716,6 +716,80 @@ int wf_patchify(float* x, float* rows, int dir, int64_t B, int64_t Cin, int64_t 
 /* (B, C, S) -> (B, S, C): the NCDHW -> channel-last transpose (proj_out's adjoint,
  * waveformer.py:289).                                                                       */
 int wf_transpose_cs(const float* in, float* out, int64_t B, int64_t C, int64_t S, void* stream);
+
+/* ======================================================================================
+ * Evaluation (ABI 22): region Dice and exact HD95 of a predicted label map against the ground
+ * truth -- what the reference's 5_compute_metrics.py takes from medpy.metric.binary.dc / hd95
+ * (and 4_predict.py:241-253 from argmax + convert_labels).  With isotropic unit spacing every
+ * surface distance is the square root of an integer, so the device side is integer only:
+ * exact squared distances in uint32, a histogram over them, and order statistics of the
+ * histogram; the one square root and the percentile interpolation are the host's
+ * (waveformer_amd.metrics).  Integer atomics only, so every output is bitwise repeatable.
+ * Volumes are (D, H, W) with D*H*W < 2^31 and D^2 + H^2 + W^2 < 2^31.
+ * ====================================================================================== */
+
+enum { WF_SRC_LABELS_U8 = 0, WF_SRC_SCORES_F16 = 1, WF_SRC_SCORES_F32 = 2 };
+
+/* "No border voxel in this mask": the value wf_surface_edt_sq writes where a mask is empty. */
+#define WF_EDT_NONE 0xFFFFFFFFu
+/* int64 values wf_hist_order_stats writes per histogram group */
+#define WF_ORDER_STATS_STRIDE 8
+
+/* Region masks of a label map (convert_labels, 5_compute_metrics.py:31-37).
+ * src: src_kind 0 = a label map (D, H, W) uint8 (C ignored); 1 / 2 = class scores
+ *   (C, D, H, W) fp16 / fp32, 1 <= C <= 8, whose label is the arg-max over C with the first
+ *   maximal index on ties and a NaN counting as the maximum (torch.argmax).
+ * region_bits: R <= 4 host ints; region r contains class c iff bit c is set (classes 0..7; a
+ *   label above 7 is in no region).  BraTS: TC {1,3} = 0x0A, WT {1,2,3} = 0x0E, ET {3} = 0x08.
+ * masks: (R, D, H, W) uint8 of 0 / 1.  labels: (D, H, W) uint8, the label map the masks were
+ *   made from; required for scores, optional (NULL) for src_kind 0.
+ * counts: R device int64, the voxel count of each mask (set, not added to).                 */
+int wf_region_masks(const void* src, int src_kind, int64_t C, const int* region_bits, int64_t R,
+                    uint8_t* masks, uint8_t* labels, int64_t* counts, int64_t D, int64_t H,
+                    int64_t W, void* stream);
+
+/* Per region r of two mask stacks a, b (R, D, H, W) uint8 (non-zero = set):
+ * counts[r] = {|a & b|, |a|, |b|}, (R, 3) device int64 -- the integers of medpy's
+ * dc = 2 |a & b| / (|a| + |b|).  One integer atomic per block and value.                     */
+int wf_overlap_counts(const uint8_t* a, const uint8_t* b, int64_t R, int64_t D, int64_t H,
+                      int64_t W, int64_t* counts, void* stream);
+
+/* Replaces, for each of M masks (M, D, H, W) uint8, medpy's surface extraction
+ * border = mask & ~binary_erosion(mask, generate_binary_structure(3, 1)) (6-neighbour cross,
+ * outside the volume = 0, so a mask voxel on a face of the volume is border) and
+ * distance_transform_edt(~border) ** 2 (medpy/metric/binary.py __surface_distances):
+ * border (M, D, H, W) uint8 of 0 / 1 and d2 (M, D, H, W) uint32, the exact squared Euclidean
+ * distance of every voxel to the nearest border voxel of the same mask, WF_EDT_NONE where the
+ * mask has no border voxel.  Separable: a row pass fused with the border, then exact min-plus
+ * passes along H and D.  workspace: wf_surface_edt_workspace_bytes(M, D, H, W) bytes.
+ * Limits: M <= 1024, W <= 4096, D and H <= 512 (the query returns -1 beyond them).      */
+int64_t wf_surface_edt_workspace_bytes(int64_t M, int64_t D, int64_t H, int64_t W);
+int wf_surface_edt_sq(const uint8_t* masks, int64_t M, int64_t D, int64_t H, int64_t W,
+                      uint8_t* border, uint32_t* d2, void* workspace, int64_t workspace_bytes,
+                      void* stream);
+
+/* Surface-distance histograms of P mask pairs (a_p, b_p), all arrays (P, D, H, W):
+ * hist[p][0][v] = #{border voxels of a_p whose squared distance to b_p's border is v} (from
+ * border_a and d2_b), hist[p][1][v] the same with the roles swapped (border_b, d2_a).
+ * hist: (P, 2, D^2 + H^2 + W^2 + 1) uint32, set, not added to.  A voxel whose distance is
+ * WF_EDT_NONE (the other mask is empty) is not counted.  medpy's hd95 is the 95th percentile
+ * of the two directions together, its asd the mean of one.                                  */
+int wf_surface_hist(const uint8_t* border_a, const uint32_t* d2_b, const uint8_t* border_b,
+                    const uint32_t* d2_a, int64_t P, int64_t D, int64_t H, int64_t W,
+                    uint32_t* hist, void* stream);
+
+/* Order statistics of G histogram groups; group g is the bin-wise sum of the `group`
+ * consecutive histograms hist[g * group ...] of nbins uint32 bins each (group 2 on
+ * wf_surface_hist's output = both directions, as hd95 wants them).  With n the group's total
+ * count and base = q_num * (n - 1) / q_den (integer division; 0 for n = 0), out[g] holds
+ * WF_ORDER_STATS_STRIDE int64: {n, highest non-empty bin, base, v0, v1, v2, v3, 0} where
+ * v_i is the bin holding the element of 0-based rank clamp(base + offsets[i], 0, n - 1) of the
+ * sorted sample, for i < nranks <= 4; -1 for an unused v_i, and for the bins when n = 0.
+ * q_num = 0 makes the offsets absolute ranks.  offsets: nranks host int64.  The ranks are
+ * derived on the device so that a caller needs no copy of n before asking.                   */
+int wf_hist_order_stats(const uint32_t* hist, int64_t G, int64_t group, int64_t nbins,
+                        int64_t q_num, int64_t q_den, const int64_t* offsets, int64_t nranks,
+                        int64_t* out, void* stream);
 
 #ifdef __cplusplus
 }

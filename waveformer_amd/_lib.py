@@ -142,9 +142,16 @@ SIGNATURES = {
     "wf_patch_merging_scatter": (_I, [_P, _I, _P, _I64, _I64, _I64, _I64, _I64, _P]),
     "wf_patchify": (_I, [_P, _P, _I, _I64, _I64, _I64, _I64, _I64, _P]),
     "wf_transpose_cs": (_I, [_P, _P, _I64, _I64, _I64, _P]),
+    # evaluation (region Dice, HD95)
+    "wf_region_masks": (_I, [_P, _I, _I64, _P, _I64, _P, _P, _P, _I64, _I64, _I64, _P]),
+    "wf_overlap_counts": (_I, [_P, _P, _I64, _I64, _I64, _I64, _P, _P]),
+    "wf_surface_edt_workspace_bytes": (_I64, [_I64, _I64, _I64, _I64]),
+    "wf_surface_edt_sq": (_I, [_P, _I64, _I64, _I64, _I64, _P, _P, _P, _I64, _P]),
+    "wf_surface_hist": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P]),
+    "wf_hist_order_stats": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _P, _P]),
 }
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 _lock = threading.Lock()
 _lib = None
 _err = None

@@ -1731,3 +1731,146 @@ def proj_out_cl(x_cl: torch.Tensor, normalize: bool, eps: float = 1e-5) -> torch
     else:
         out.copy_(x_cl)
     return out.permute(0, 4, 1, 2, 3)
+
+
+# ------------------------------------------------------------------------------------------
+# evaluation: region masks, overlap counts, surface distances (waveformer_amd.metrics)
+# ------------------------------------------------------------------------------------------
+EDT_NONE = 0xFFFFFFFF        # wf_surface_edt_sq: the mask has no border voxel
+ORDER_STATS_STRIDE = 8       # int64 values per histogram group of wf_hist_order_stats
+_SCORE_KINDS = {torch.float16: 1, torch.float32: 2}
+
+
+def surface_hist_bins(size: Sequence[int]) -> int:
+    """Bins of a surface-distance histogram over a (D, H, W) volume: every squared distance."""
+    D, H, W = (int(v) for v in size)
+    return D * D + H * H + W * W + 1
+
+
+def region_masks(src: torch.Tensor, region_bits: Sequence[int],
+                 out: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None
+                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Region masks of a label map (D, H, W) uint8, or of class scores (C, D, H, W) fp16 / fp32
+    by their arg-max (wf_region_masks).  region_bits[r] has bit c set iff region r contains
+    class c.  Returns (masks (R, D, H, W) uint8, the label map, counts (R,) int64); `out` and
+    `counts` let a caller place the masks and the counts inside larger buffers."""
+    if not isinstance(src, torch.Tensor):
+        raise TypeError(f"region_masks: expected a tensor, got {type(src)}")
+    if src.dim() == 3:
+        _check(src, "labels", dtype=torch.uint8)
+        kind, C, labels = 0, 0, None
+        size = tuple(src.shape)
+    elif src.dim() == 4:
+        if src.dtype not in _SCORE_KINDS:
+            raise TypeError(f"region_masks: scores must be fp16 or fp32, got {src.dtype}")
+        _check(src, "scores", dtype=src.dtype)
+        kind, C = _SCORE_KINDS[src.dtype], int(src.shape[0])
+        size = tuple(src.shape[1:])
+        labels = torch.empty(size, dtype=torch.uint8, device=src.device)
+    else:
+        raise ValueError(f"region_masks: expected (D, H, W) labels or (C, D, H, W) scores, got "
+                         f"{tuple(src.shape)}")
+    R = len(region_bits)
+    if out is None:
+        out = torch.empty((R,) + size, dtype=torch.uint8, device=src.device)
+    else:
+        _check(out, "out", dtype=torch.uint8)
+        if tuple(out.shape) != (R,) + size:
+            raise ValueError(f"region_masks: out {tuple(out.shape)} != {(R,) + size}")
+    if counts is None:
+        counts = torch.empty((R,), dtype=torch.int64, device=src.device)
+    else:
+        _check(counts, "counts", dtype=torch.int64)
+        if counts.numel() != R:
+            raise ValueError(f"region_masks: counts has {counts.numel()} elements, need {R}")
+    bits = (ctypes.c_int * max(R, 1))(*[int(b) for b in region_bits])
+    _lib.call("wf_region_masks", src.data_ptr(), kind, C, bits, R, out.data_ptr(), _ptr(labels),
+              counts.data_ptr(), *size, _stream())
+    return out, (src if labels is None else labels), counts
+
+
+def overlap_counts(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None
+                   ) -> torch.Tensor:
+    """(R, 3) int64 {|a & b|, |a|, |b|} per region of two mask stacks (R, D, H, W) uint8."""
+    _check(a, "a", dtype=torch.uint8)
+    _check(b, "b", dtype=torch.uint8)
+    if a.dim() != 4 or a.shape != b.shape:
+        raise ValueError(f"overlap_counts: need two (R, D, H, W) stacks, got {tuple(a.shape)} "
+                         f"and {tuple(b.shape)}")
+    R = int(a.shape[0])
+    if out is None:
+        out = torch.empty((R, 3), dtype=torch.int64, device=a.device)
+    else:
+        _check(out, "out", dtype=torch.int64)
+        if out.numel() != R * 3:
+            raise ValueError(f"overlap_counts: out has {out.numel()} elements, need {R * 3}")
+    _lib.call("wf_overlap_counts", a.data_ptr(), b.data_ptr(), *a.shape, out.data_ptr(),
+              _stream())
+    return out
+
+
+def surface_edt_sq(masks: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Of each mask of (M, D, H, W) uint8: its border (mask & ~erosion by the 6-neighbour cross,
+    the outside of the volume counting as 0) as uint8, and the exact squared Euclidean distance
+    of every voxel to the nearest border voxel as uint32, EDT_NONE where the mask has no border
+    voxel (wf_surface_edt_sq)."""
+    _check(masks, "masks", dtype=torch.uint8)
+    if masks.dim() != 4:
+        raise ValueError(f"surface_edt_sq: expected (M, D, H, W), got {tuple(masks.shape)}")
+    M, D, H, W = (int(v) for v in masks.shape)
+    nbytes = _lib.query("wf_surface_edt_workspace_bytes", M, D, H, W)
+    if nbytes < 0:
+        raise RuntimeError("wf_surface_edt_workspace_bytes failed: "
+                           + _lib.load().wf_last_error().decode(errors="replace"))
+    border = torch.empty_like(masks)
+    d2 = torch.empty(masks.shape, dtype=torch.uint32, device=masks.device)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=masks.device)
+    _lib.call("wf_surface_edt_sq", masks.data_ptr(), M, D, H, W, border.data_ptr(),
+              d2.data_ptr(), ws.data_ptr(), nbytes, _stream())
+    return border, d2
+
+
+def surface_hist(border_a: torch.Tensor, d2_b: torch.Tensor, border_b: torch.Tensor,
+                 d2_a: torch.Tensor) -> torch.Tensor:
+    """(P, 2, D^2 + H^2 + W^2 + 1) uint32 histograms of the squared surface distances of P mask
+    pairs: [p, 0] counts a_p's border voxels by their distance to b_p's border, [p, 1] the
+    reverse.  All four inputs are (P, D, H, W), as surface_edt_sq returns them."""
+    _check(border_a, "border_a", dtype=torch.uint8)
+    _check(border_b, "border_b", dtype=torch.uint8)
+    _check(d2_a, "d2_a", dtype=torch.uint32)
+    _check(d2_b, "d2_b", dtype=torch.uint32)
+    if border_a.dim() != 4 or not (border_a.shape == border_b.shape == d2_a.shape == d2_b.shape):
+        raise ValueError("surface_hist: need four (P, D, H, W) tensors of one shape")
+    P, D, H, W = (int(v) for v in border_a.shape)
+    hist = torch.empty((P, 2, surface_hist_bins((D, H, W))), dtype=torch.uint32,
+                       device=border_a.device)
+    _lib.call("wf_surface_hist", border_a.data_ptr(), d2_b.data_ptr(), border_b.data_ptr(),
+              d2_a.data_ptr(), P, D, H, W, hist.data_ptr(), _stream())
+    return hist
+
+
+def hist_order_stats(hist: torch.Tensor, offsets: Sequence[int], q: Tuple[int, int] = (0, 1),
+                     group: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Order statistics of histograms (..., nbins) uint32, `group` consecutive ones summed into
+    one sample: (G, 8) int64 rows {n, highest non-empty bin, base, v0..v3, 0} with
+    base = q[0] * (n - 1) // q[1] and v_i the bin at 0-based rank clamp(base + offsets[i], 0,
+    n - 1) (wf_hist_order_stats).  q = (0, 1) makes the offsets absolute ranks."""
+    _check(hist, "hist", dtype=torch.uint32)
+    nbins = int(hist.shape[-1])
+    nh = hist.numel() // nbins
+    if nh % group:
+        raise ValueError(f"hist_order_stats: {nh} histograms are no multiple of group {group}")
+    G = nh // group
+    if len(offsets) > 4:
+        raise ValueError("hist_order_stats: at most 4 ranks")
+    if out is None:
+        out = torch.empty((G, ORDER_STATS_STRIDE), dtype=torch.int64, device=hist.device)
+    else:
+        _check(out, "out", dtype=torch.int64)
+        if out.numel() != G * ORDER_STATS_STRIDE:
+            raise ValueError(f"hist_order_stats: out has {out.numel()} elements, need "
+                             f"{G * ORDER_STATS_STRIDE}")
+    offs = (ctypes.c_int64 * max(len(offsets), 1))(*[int(o) for o in offsets])
+    _lib.call("wf_hist_order_stats", hist.data_ptr(), G, int(group), nbins, int(q[0]), int(q[1]),
+              offs, len(offsets), out.data_ptr(), _stream())
+    return out
