@@ -297,7 +297,14 @@ constexpr int TQ_BYTES = TBLN * 16;
 // pay the cross-group max exchange (two ds_bpermute round trips on the critical path), the
 // alpha exponential and the o / l rescale.  The exponentials of a kept tile are at most
 // 2^kTau; the normalisation o / l is the same quotient, so this changes only fp32 rounding.
+// The exponentials become MFMA operands, so 2^tau must be finite in the operand kind: bf16 has
+// fp32's range, but fp16 ends at 65504 and a kept score in (mrun + 15.99965, mrun + 16] gave an
+// inf probability and a NaN row.  fp16 operands therefore keep a tile only up to 2^15
+// (tests/test_gpu_attention_softmax.py, f16_band).
 constexpr float kTau = 16.0f;
+constexpr float kTauFp16 = 15.0f;
+template <int P>
+constexpr float tau = P == PREC_FP16 ? kTauFp16 : kTau;
 }  // namespace tbl
 
 // ---- q / k / v computed in the core (attn_tbl_kernel_fused) -----------------------------------
@@ -580,7 +587,7 @@ __device__ __forceinline__ void attn_tbl_tiles(const void* __restrict__ qkv,
         for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
           for (int i = (kt == 0 ? 1 : 0); i < 4; ++i) lmax[u] = fmaxf(lmax[u], s[u][kt][i]);
-        big = big || lmax[u] > mrun[u] + kTau;
+        big = big || lmax[u] > mrun[u] + tau<P>;
       }
       if (__builtin_amdgcn_ballot_w64(big) != 0) {  // wave-uniform
 #pragma unroll
