@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define WF_ABI_VERSION 22
+#define WF_ABI_VERSION 23
 
 enum { WF_PREC_BF16 = 0, WF_PREC_BF16X3 = 1, WF_PREC_FP16 = 2 };
 
@@ -318,6 +318,26 @@ int wf_hf_refine_fwd(const float* const* details, int64_t ldb, const float* dw_w
                      const float* pw_w, const float* pw_b, int sigmoid, float* out,
                      void* workspace, int64_t B, int64_t C, int64_t D, int64_t H, int64_t W,
                      void* stream);
+
+/* Backward of wf_hf_refine_fwd (ABI 23; training through HFRefinementRes,
+ * network_models/idwt_upsample.py:39-50 under autograd).  details, ldb, the six parameters, eps
+ * and sigmoid as in the forward; moments: the forward's workspace after the call, (7, B, C, 2)
+ * fp64 {sum, sum of squares} of the depthwise conv's output, read only; gy: the output
+ * gradient (7, B, D, H, W, C), dense.  Writes every element of gx (7, B, D, H, W, C), g_dw_w
+ * (C, 27), g_dw_b (C), g_in_w (C), g_in_b (C), g_pw_w (C, C), g_pw_b (C); the parameter
+ * gradients are summed over the 7 tensors and the batch.  g_dw_b is written as exact zeros:
+ * the InstanceNorm removes the conv's mean, so the sum it stands for is 0 in exact arithmetic.
+ * fp32 arithmetic (g_pw_w on wf_gemm_tn's fp32-faithful bf16x3); no atomics: every sum over
+ * workgroups is per-workgroup partials added in a fixed order, two calls on the same inputs
+ * are bitwise identical.  workspace: wf_hf_refine_bwd_workspace_bytes(B, C, D, H, W) bytes
+ * (0 for an unsupported shape).  C % 4 == 0, 4 <= C <= 256, any D, H, W >= 1.                */
+int64_t wf_hf_refine_bwd_workspace_bytes(int64_t B, int64_t C, int64_t D, int64_t H, int64_t W);
+int wf_hf_refine_bwd(const float* const* details, int64_t ldb, const float* dw_w,
+                     const float* dw_b, const float* in_w, const float* in_b, float eps,
+                     const float* pw_w, const float* pw_b, int sigmoid, const double* moments,
+                     const float* gy, float* gx, float* g_dw_w, float* g_dw_b, float* g_in_w,
+                     float* g_in_b, float* g_pw_w, float* g_pw_b, void* workspace, int64_t B,
+                     int64_t C, int64_t D, int64_t H, int64_t W, void* stream);
 
 /* Backward of y = LeakyReLU(slope)((a - mean_a) * rstd_a + r') (wf_norm_act_cl; training of
  * UnetResBlock / UnetBasicBlock): dz = dy * (y > 0 ? 1 : slope),

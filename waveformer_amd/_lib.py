@@ -79,6 +79,9 @@ SIGNATURES = {
     "wf_hf_refine_workspace_bytes": (_I64, [_I64, _I64]),
     "wf_hf_refine_fwd": (_I, [_P, _I64, _P, _P, _P, _P, _F, _P, _P, _I, _P, _P, _I64, _I64,
                               _I64, _I64, _I64, _P]),
+    "wf_hf_refine_bwd_workspace_bytes": (_I64, [_I64] * 5),
+    "wf_hf_refine_bwd": (_I, [_P, _I64, _P, _P, _P, _P, _F, _P, _P, _I, _P, _P, _P, _P, _P, _P,
+                              _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _P]),
     "wf_norm_act_cl": (_I, [_P, _I64, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _F, _P]),
     "wf_upsample_trilinear_cl": (_I, [_P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64,
                                       _I, _P]),
@@ -151,7 +154,7 @@ SIGNATURES = {
     "wf_hist_order_stats": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _P, _P]),
 }
 
-ABI_VERSION = 22
+ABI_VERSION = 23
 _lock = threading.Lock()
 _lib = None
 _err = None

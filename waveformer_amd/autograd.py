@@ -118,6 +118,19 @@ def idwt3d_haar(ll: torch.Tensor, details: Sequence[Dict[str, torch.Tensor]]) ->
     return torch.ops.waveformer.idwt3d(ll, [dct[k] for dct in details for k in DETAIL_KEYS])
 
 
+def hf_refine(details: Dict[str, torch.Tensor], mod) -> Dict[str, torch.Tensor]:
+    """Differentiable HFRefinementRes `mod` over the 7 detail tensors of one level
+    (waveformer::hf_refine: one fused forward, one fused backward) -> the refined tensors as
+    channel-last (B, C, D, H, W) views of one stacked buffer (what idwt3d_haar / waverec3 read)."""
+    from . import library  # noqa: F401
+    c1, nrm, c2 = mod.conv1, mod.norm, mod.conv2
+    out, _ = torch.ops.waveformer.hf_refine(
+        [details[k] for k in DETAIL_KEYS], c1.weight, c1.bias, nrm.weight, nrm.bias,
+        float(nrm.eps), c2.weight, c2.bias, mod.sigmoid is not None)
+    parts = out.unbind(0)  # one stack in backward
+    return {k: parts[i].permute(0, 4, 1, 2, 3) for i, k in enumerate(DETAIL_KEYS)}
+
+
 def wavedec3(x: torch.Tensor, wavelet, level: int) -> List:
     """Differentiable ptwt.wavedec3(x, wavelet, mode='zero', level=level) for db1..db4 ->
     [LL, dict_coarsest, ..., dict_finest]: a chain of waveformer::wavedec3_level."""

@@ -15,6 +15,7 @@ them (attention.py:83-104, wave_helper.py:349 / :470-512, idwt_upsample.py:160).
   waveformer::msfuse         the multi-scale trilinear fuse + shortcut (+ norm2 statistics)
   waveformer::ccf_ffn        norm2 + CCF_FFN + the Q4 double residual
   waveformer::patch_merging  PatchMerging(V2) (Q3 sub-lattices)
+  waveformer::hf_refine      HFRefinementRes over the 7 detail tensors of a level (config 5)
 
 Each op's CUDA kernel is the HIP path of waveformer_amd.ops; `register_fake` gives output
 shapes from input shapes alone; `register_autograd` wires the HIP backward kernels
@@ -775,17 +776,80 @@ def _merge_bwd(ctx, gout):
 patch_merging.register_autograd(_merge_bwd, setup_context=_merge_setup)
 
 
+# ------------------------------------------------------------------------------------------
+# a12: HFRefinementRes over the 7 detail tensors of a level (config 5)
+# ------------------------------------------------------------------------------------------
+@torch.library.custom_op("waveformer::hf_refine", mutates_args=(), device_types="cuda")
+def hf_refine(details: List[Tensor], dw_w: Tensor, dw_b: Tensor, in_w: Tensor, in_b: Tensor,
+              eps: float, pw_w: Tensor, pw_b: Tensor, sigmoid: bool) -> Tuple[Tensor, Tensor]:
+    """x_k * sigmoid(conv2(relu(norm(conv1(x_k))))) of the 7 (B, C, D, H, W) detail tensors
+    (DETAIL_KEYS order; HFRefinementRes.forward, idwt_upsample.py:39-50) -> (out (7, B, D, H,
+    W, C), one stacked channel-last buffer; moments (7, B, C, 2) fp64, the InstanceNorm sums
+    the backward reads, not differentiable)."""
+    return ops._hf_refine_raw(list(details), dw_w, dw_b, in_w, in_b, eps, pw_w, pw_b, sigmoid)
+
+
+@hf_refine.register_fake
+def _(details, dw_w, dw_b, in_w, in_b, eps, pw_w, pw_b, sigmoid):
+    B, C, D, H, W = details[0].shape
+    return (details[0].new_empty((7, B, D, H, W, C)),
+            details[0].new_empty((7, B, C, 2), dtype=torch.float64))
+
+
+def _hf_setup(ctx, inputs, output):
+    details, dw_w, dw_b, in_w, in_b, eps, pw_w, pw_b, sigmoid = inputs
+    ctx.meta = (float(eps), bool(sigmoid))
+    ctx.set_materialize_grads(False)  # no zero gradient for the moments output
+    ctx.save_for_backward(dw_w, dw_b, in_w, in_b, pw_w, pw_b, output[1], *details)
+
+
+@torch.library.custom_op("waveformer::hf_refine_backward", mutates_args=(), device_types="cuda")
+def hf_refine_backward(gout: Tensor, details: List[Tensor], dw_w: Tensor, dw_b: Tensor,
+                       in_w: Tensor, in_b: Tensor, eps: float, pw_w: Tensor, pw_b: Tensor,
+                       sigmoid: bool, moments: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor,
+                                                                Tensor, Tensor, Tensor]:
+    """(gx (7, B, D, H, W, C), d dw_w, d dw_b, d in_w, d in_b, d pw_w, d pw_b) of hf_refine
+    from its saved moments (wf_hf_refine_bwd: the fused gate-chain kernel, the depthwise
+    adjoint and weight gradient, d pw_w on wf_gemm_tn; parameter gradients summed over the 7
+    tensors and the batch)."""
+    return ops.hf_refine_bwd(list(details), dw_w, dw_b, in_w, in_b, eps, pw_w, pw_b, sigmoid,
+                             moments, _f32(gout))
+
+
+@hf_refine_backward.register_fake
+def _(gout, details, dw_w, dw_b, in_w, in_b, eps, pw_w, pw_b, sigmoid, moments):
+    return (torch.empty_like(gout, memory_format=torch.contiguous_format),
+            *[torch.empty_like(p) for p in (dw_w, dw_b, in_w, in_b, pw_w, pw_b)])
+
+
+def _hf_bwd(ctx, gout, _gmoments):
+    dw_w, dw_b, in_w, in_b, pw_w, pw_b, moments, *details = ctx.saved_tensors
+    eps, sigmoid = ctx.meta
+    if gout is None:  # grads are not materialized (see _hf_setup)
+        B, C, D, H, W = details[0].shape
+        gout = details[0].new_zeros((7, B, D, H, W, C))
+    gx, *gp = torch.ops.waveformer.hf_refine_backward(gout, details, dw_w, dw_b, in_w, in_b, eps,
+                                                      pw_w, pw_b, sigmoid, moments)
+    # one stacked gradient, unbound once: the 7 detail gradients are views of it
+    gd = [t.permute(0, 4, 1, 2, 3) for t in gx.unbind(0)]
+    return (gd, gp[0], gp[1], gp[2], gp[3], None, gp[4], gp[5], None)
+
+
+hf_refine.register_autograd(_hf_bwd, setup_context=_hf_setup)
+
+
 OPS = {"dwt3d": dwt3d, "idwt3d": idwt3d, "wavedec3_level": wavedec3_level,
        "waverec3_level": waverec3_level, "window_attn": window_attn,
        "window_attn_levels": window_attn_levels, "msfuse": msfuse, "ccf_ffn": ccf_ffn,
-       "patch_merging": patch_merging}
+       "patch_merging": patch_merging, "hf_refine": hf_refine}
 # the backward kernels are ops too, so AOT autograd can trace a backward graph through them
 BACKWARD_OPS = {"dwt3d_backward": dwt3d_backward, "idwt3d_backward": idwt3d_backward,
                 "wavedec3_level_backward": wavedec3_level_backward,
                 "waverec3_level_backward": waverec3_level_backward,
                 "window_attn_backward": window_attn_backward, "msfuse_backward": msfuse_backward,
                 "ccf_ffn_backward": ccf_ffn_backward,
-                "patch_merging_backward": patch_merging_backward}
+                "patch_merging_backward": patch_merging_backward,
+                "hf_refine_backward": hf_refine_backward}
 
 
 # CPU: no kernel -- the product path has no CPU or eager-PyTorch fallback; a CPU tensor fails

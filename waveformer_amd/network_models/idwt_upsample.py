@@ -1,8 +1,10 @@
 """IDWT decoder block.
 
 Mirrors network_models/idwt_upsample.py (HFRefinementRes :12-50, UnetrIDWTBlock :53-166):
-same constructor and state_dict keys.  HFRefinementRes runs as one fused HIP call per level
-at inference (ops.hf_refine; PyTorch modules under autograd).  The wavelet synthesis (ptwt.waverec3, :160) and the
+same constructor and state_dict keys.  HFRefinementRes runs as one fused HIP call per level:
+ops.hf_refine at inference, waveformer::hf_refine with its fused HIP backward under autograd
+(the per-tensor module forward remains for CPU tensors, unsupported shapes and direct calls).
+The wavelet synthesis (ptwt.waverec3, :160) and the
 concatenation with the skip (:163) run as one wf_idwt3d_haar launch that writes straight into
 the first half of the concatenated buffer (with the skip in the same kernel,
 wf_idwt3d_haar_cl_cat); the surrounding convolutions run on the HIP conv3d_k3 kernel and the
@@ -36,18 +38,22 @@ class HFRefinementRes(nn.Module):
         self.conv2 = nn.Conv3d(in_channels, in_channels, kernel_size=1, bias=True)
         self.sigmoid = nn.Sigmoid() if hf_config.get('use_sigmoid', True) else None
 
-    def fast_ok(self, x) -> bool:
-        """The fused HIP path (ops.hf_refine, inference) covers this module: depthwise 3^3
+    def train_ok(self, x) -> bool:
+        """The fused HIP kernels (wf_hf_refine_fwd / _bwd) cover this module: depthwise 3^3
         conv with bias, InstanceNorm3d(affine, no running stats), 1x1 conv with bias."""
         c1, n, c2 = self.conv1, self.norm, self.conv2
         return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 5
-                and not (torch.is_grad_enabled() and (
-                    x.requires_grad or any(p.requires_grad for p in self.parameters())))
                 and x.shape[1] % 4 == 0 and x.shape[1] <= 256
                 and c1.kernel_size == (3, 3, 3) and c1.padding == (1, 1, 1)
                 and c1.groups == c1.in_channels and c1.bias is not None
                 and n.affine and not n.track_running_stats
                 and c2.kernel_size == (1, 1, 1) and c2.bias is not None)
+
+    def fast_ok(self, x) -> bool:
+        """train_ok with nothing to differentiate: the inference path (ops.hf_refine)."""
+        return (not (torch.is_grad_enabled() and (
+            x.requires_grad or any(p.requires_grad for p in self.parameters())))
+                and self.train_ok(x))
 
     def forward(self, x):
         # the convs through wfa.conv_train (HIP depthwise, GEMM 1x1; modules for CPU tensors)
@@ -82,9 +88,12 @@ class UnetrIDWTBlock(nn.Module):
     def forward(self, inp, skip, hf_coeffs):
         inp = self.conv_lf_block(inp)
         if self.hf_refinement:
-            # inference: the 7 details of a level in one fused HIP call (ops.hf_refine)
+            # the 7 details of a level in one fused HIP call: ops.hf_refine at inference,
+            # waveformer::hf_refine (fused backward) under autograd
             hf_coeffs = tuple(
                 ops.hf_refine(d, self.hf_ref[i]) if self.hf_ref[i].fast_ok(d["aad"])
+                else wfa.hf_refine(d, self.hf_ref[i])
+                if torch.is_grad_enabled() and self.hf_ref[i].train_ok(d["aad"])
                 else {k: self.hf_ref[i](d[k]) for k in d}
                 for i, d in enumerate(hf_coeffs))
         wname = str(getattr(self.wavelet, "name", self.wavelet))

@@ -772,9 +772,22 @@ def hf_refine(details: Dict[str, torch.Tensor], mod) -> Dict[str, torch.Tensor]:
     norm + ReLU + 1x1 conv + sigmoid + product).  details: {key: (B, C, D, H, W)} channel-last
     views (the DWT's detail bands); returns the refined tensors the same way, as views of one
     (7, B, D, H, W, C) buffer (what idwt3d_haar reads)."""
-    ts = [details[k] for k in DETAIL_KEYS]
+    c1, nrm, c2 = mod.conv1, mod.norm, mod.conv2
+    out, _ = _hf_refine_raw([details[k] for k in DETAIL_KEYS], c1.weight, c1.bias, nrm.weight,
+                            nrm.bias, float(nrm.eps), c2.weight, c2.bias, mod.sigmoid is not None)
+    return {k: out[i].permute(0, 4, 1, 2, 3) for i, k in enumerate(DETAIL_KEYS)}
+
+
+_HF_PARAMS = ("conv1.weight", "conv1.bias", "norm.weight", "norm.bias", "conv2.weight",
+              "conv2.bias")
+
+
+def _hf_details(ts: Sequence[torch.Tensor], who: str) -> List[torch.Tensor]:
+    """The 7 detail tensors as the HF-refinement kernels read them: (B, C, D, H, W) views of
+    dense channel-last samples with one common batch stride (copies where they are not)."""
+    if len(ts) != 7:
+        raise ValueError(f"{who}: 7 detail tensors expected, got {len(ts)}")
     B, C, D, H, W = ts[0].shape
-    P = D * H * W
 
     def dense_cl(t):  # (b, c, z, y, x) at b*s0 + ((z*H + y)*W + x)*C + c
         st = t.stride()
@@ -784,21 +797,58 @@ def hf_refine(details: Dict[str, torch.Tensor], mod) -> Dict[str, torch.Tensor]:
         ts = [t.contiguous(memory_format=torch.channels_last_3d) for t in ts]
     for t in ts:
         if tuple(t.shape) != (B, C, D, H, W):
-            raise ValueError("hf_refine: the 7 detail tensors must share one shape")
+            raise ValueError(f"{who}: the 7 detail tensors must share one shape")
         _check(t, "detail", contiguous=False)
-    c1, nrm, c2 = mod.conv1, mod.norm, mod.conv2
-    for prm, nm in ((c1.weight, "conv1.weight"), (c1.bias, "conv1.bias"), (nrm.weight, "norm.weight"),
-                    (nrm.bias, "norm.bias"), (c2.weight, "conv2.weight"), (c2.bias, "conv2.bias")):
+    return ts
+
+
+def _hf_refine_raw(details: Sequence[torch.Tensor], dw_w, dw_b, in_w, in_b, eps: float, pw_w,
+                   pw_b, sigmoid: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """wf_hf_refine_fwd over the 7 detail tensors (DETAIL_KEYS order) -> (out (7, B, D, H, W, C),
+    moments (7, B, C, 2) fp64 {sum, sum of squares} of the depthwise conv's output: the
+    kernel's workspace, what hf_refine_bwd reads)."""
+    ts = _hf_details(details, "hf_refine")
+    B, C, D, H, W = ts[0].shape
+    for prm, nm in zip((dw_w, dw_b, in_w, in_b, pw_w, pw_b), _HF_PARAMS):
         _check(prm, nm)
     out = torch.empty((7, B, D, H, W, C), dtype=torch.float32, device=ts[0].device)
     ws = torch.empty(_lib.query("wf_hf_refine_workspace_bytes", B, C), dtype=torch.uint8,
                      device=out.device)
     ptrs = (ctypes.c_void_p * 7)(*[t.data_ptr() for t in ts])
-    _lib.call("wf_hf_refine_fwd", ptrs, ts[0].stride(0), c1.weight.data_ptr(), c1.bias.data_ptr(),
-              nrm.weight.data_ptr(), nrm.bias.data_ptr(), float(nrm.eps), c2.weight.data_ptr(),
-              c2.bias.data_ptr(), int(mod.sigmoid is not None), out.data_ptr(), ws.data_ptr(),
-              B, C, D, H, W, _stream())
-    return {k: out[i].permute(0, 4, 1, 2, 3) for i, k in enumerate(DETAIL_KEYS)}
+    _lib.call("wf_hf_refine_fwd", ptrs, ts[0].stride(0), dw_w.data_ptr(), dw_b.data_ptr(),
+              in_w.data_ptr(), in_b.data_ptr(), float(eps), pw_w.data_ptr(), pw_b.data_ptr(),
+              int(bool(sigmoid)), out.data_ptr(), ws.data_ptr(), B, C, D, H, W, _stream())
+    return out, ws.view(torch.float64).view(7, B, C, 2)
+
+
+def hf_refine_bwd(details: Sequence[torch.Tensor], dw_w, dw_b, in_w, in_b, eps: float, pw_w,
+                  pw_b, sigmoid: bool, moments: torch.Tensor, gy: torch.Tensor):
+    """Backward of _hf_refine_raw (wf_hf_refine_bwd): gy (7, B, D, H, W, C) the output
+    gradient, moments the forward's -> (gx (7, B, D, H, W, C), g_dw_w, g_dw_b, g_in_w, g_in_b,
+    g_pw_w, g_pw_b), the parameter gradients shaped like the parameters and summed over the 7
+    tensors and the batch (g_dw_b: exact zeros, the InstanceNorm removes the conv's mean)."""
+    ts = _hf_details(details, "hf_refine_bwd")
+    B, C, D, H, W = ts[0].shape
+    prms = (dw_w, dw_b, in_w, in_b, pw_w, pw_b)
+    for prm, nm in zip(prms, _HF_PARAMS):
+        _check(prm, nm)
+    _check(gy, "gy")
+    if tuple(gy.shape) != (7, B, D, H, W, C):
+        raise ValueError(f"hf_refine_bwd: gy {tuple(gy.shape)}, expected {(7, B, D, H, W, C)}")
+    if (moments.dtype != torch.float64 or tuple(moments.shape) != (7, B, C, 2)
+            or not moments.is_contiguous() or moments.device != gy.device):
+        raise ValueError("hf_refine_bwd: moments must be the forward's (7, B, C, 2) fp64 buffer")
+    dev = gy.device
+    gx = torch.empty_like(gy)
+    grads = [torch.empty_like(p) for p in prms]
+    ws = torch.empty(_lib.query("wf_hf_refine_bwd_workspace_bytes", B, C, D, H, W),
+                     dtype=torch.uint8, device=dev)
+    ptrs = (ctypes.c_void_p * 7)(*[t.data_ptr() for t in ts])
+    _lib.call("wf_hf_refine_bwd", ptrs, ts[0].stride(0), dw_w.data_ptr(), dw_b.data_ptr(),
+              in_w.data_ptr(), in_b.data_ptr(), float(eps), pw_w.data_ptr(), pw_b.data_ptr(),
+              int(bool(sigmoid)), moments.data_ptr(), gy.data_ptr(), gx.data_ptr(),
+              *[g.data_ptr() for g in grads], ws.data_ptr(), B, C, D, H, W, _stream())
+    return (gx, *grads)
 
 
 def to_cl(x: torch.Tensor) -> torch.Tensor:
