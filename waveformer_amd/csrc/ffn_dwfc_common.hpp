@@ -51,10 +51,11 @@ inline int ffn_dbg_env() {
 int launch_ffn_dwfc_s1(const DwFcArgs& a, int prec, hipStream_t s);
 // three VALU waves per SIMD on 4 x 8 tiles, two barriers per plane (ffn_dwfc_tb.hip)
 int launch_ffn_dwfc_tb4(const DwFcArgs& a, int prec, hipStream_t s);
-// the same for C = 96, hidden = 384 (4 x 4 tiles, one plane buffer, fc weight hi in LDS):
+// the same for C = 96, hidden = 384 (4 x 4 tiles, depthwise inputs loaded straight into
+// registers, two h2 tiles and the fc weight hi in LDS):
 // ffn_dwfc2_tb for fp32 h1 where ffn_dwfc2_tb_fits, else ffn_dwfc2_kernel; sets ZS
 int launch_ffn_dwfc2(const DwFcArgs& a, int prec, hipStream_t s);
-// three depthwise waves + one staging / fc wave per SIMD (ffn_dwfc2_tb.hip); ZS set by the caller
+// three depthwise waves + one fc wave per SIMD (ffn_dwfc2_tb.hip); ZS set by the caller
 int launch_ffn_dwfc2_tb(const DwFcArgs& a, int prec, hipStream_t s);
 // ---- the whole CCF_FFN + norm2 + Q4 residual in one kernel for C = 48, hidden = 192: the
 // haloed h1 plane is computed in LDS from the x rows (pw MFMA + LN1 + GELU), never stored
@@ -62,7 +63,9 @@ int launch_ffn_fused(const DwFcArgs& a, int prec, hipStream_t s);
 // The tb kernels address x, out and one h1 plane through 32-bit buffer byte offsets, and mark
 // halo positions outside the volume with the offset BUF_OOR = 2^31, which must lie beyond the
 // plane descriptor's range: x / out (C channels) and one haloed plane (HID channels) stay
-// below 2 GiB.  Larger shapes take ffn_dwfc_sb / ffn_dwfc2_kernel, which have no such limit.
+// below 2 GiB.  (ffn_dwfc2_tb's D waves load the plane directly through such a descriptor and
+// mark "outside" with a descriptor range of 0 instead.)  Larger shapes take ffn_dwfc_sb /
+// ffn_dwfc2_kernel, which have no such limit.
 inline bool ffn_dwfc_tb4_fits(const DwFcArgs& a) {
   return (int64_t)a.B * a.D * a.H * a.W * 48 * 4 < ((int64_t)1 << 31) &&
          (int64_t)a.H * a.W * 192 * 4 < ((int64_t)1 << 31);
