@@ -65,11 +65,12 @@ def test_dwt_haar_vs_oracle(C_, ln):
         assert C.rel_l2(det[k], det_ref[k]) <= 1e-5, k
 
 
-@pytest.mark.parametrize("C_", [8, 48, 96, 192, 40])
+@pytest.mark.parametrize("C_", [8, 48, 96, 192, 40, 4, 16, 32, 128, 256, 320])
 @pytest.mark.parametrize("ln", [False, True])
 def test_dwt_haar_ll_only_bitwise(C_, ln):
     """wf_dwt3d_haar_fwd_ll (the Blocks whose detail bands are discarded) is bitwise band 0 of
-    the 8-band kernel, with and without the fused norm1."""
+    the 8-band kernel, with and without the fused norm1.  C = 4, 16, 32, 128, 256 take the
+    row groups of 1, 4, 8, 32, 64 lanes with one float4 per lane, C = 320 64 lanes with two."""
     from waveformer_amd import ops
     x = cuda(seeded_randn((2, 8, 6, 10, C_), 11) * 3 + 0.5)
     lnp = (cuda(seeded_randn((C_,), 12) * 0.2 + 1), cuda(seeded_randn((C_,), 13) * 0.1), 1e-6)

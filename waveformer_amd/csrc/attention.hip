@@ -23,15 +23,10 @@ namespace wf {
 
 constexpr int kQB = 64;  // queries per workgroup (16 per wave)
 
-// XCD-aware decode of the 1-D grid.  Workgroups are dealt round-robin over the 8 XCDs (linear
-// id L runs on XCD L % 8), so the query tiles of one (window, head) -- which all stage the same
-// K / V rows -- would land on 8 different XCDs and each XCD's L2 would fetch those rows again.
-// Logical id t = the L-th slot of XCD L % 8 in a contiguous split keeps consecutive t (the
-// query tiles of one (window, head)) on one XCD.
+// XCD-contiguous decode of the 1-D grid: the query tiles of one (window, head), which all stage
+// the same K / V rows, run on one XCD instead of fetching those rows into 8 L2s
 __device__ __forceinline__ void attn_block(int gx, int heads, int& qb, int& h, int64_t& bw) {
-  const int64_t L = blockIdx.x, nb = gridDim.x;
-  const int64_t xcd = L & 7, q8 = nb >> 3, r8 = nb & 7;
-  int64_t t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (L >> 3);
+  int64_t t = xcd_block_id<int64_t>();
   qb = (int)(t % gx);
   t /= gx;
   h = (int)(t % heads);

@@ -10,11 +10,10 @@
 // below do the same: 3 butterfly stages without scaling, then one multiply by 2^-1.5.
 //
 // HBM roofline: both kernels are pure streaming (8 fp32 in -> 8 fp32 out per 2x2x2 cube).
+#include "haar.hpp"
 #include "rowgroup.hpp"
 
 namespace wf {
-
-constexpr float kHaar3 = 0.35355339059327373f;  // (1/sqrt 2)^3
 
 // Forward: one row group per OUTPUT position; lanes over channels.
 // x (B,D,H,W,C) channel-last -> bands (8,B,D/2,H/2,W/2,C); band k bits (bd,bh,bw) = k>>2,k>>1,k.
@@ -75,7 +74,7 @@ __global__ __launch_bounds__(256) void dwt3d_haar_fwd_kernel(
         for (int j = 0; j < V; ++j) v[n][j] = (v[n][j] - mean) * rstd * gw[j] + gb[j];
       }
     }
-    // butterflies along x (n bit0), y (bit1), z (bit2); slot index becomes the band index
+    // haar_butterfly (haar.hpp) over the V slots; slot index becomes the band index
 #pragma unroll
     for (int bit = 1; bit < 8; bit <<= 1) {
 #pragma unroll
@@ -129,6 +128,24 @@ __device__ __forceinline__ float idwt_coef(const IdwtArgs& a, int l, int k, int 
                       ((int64_t)y * Wl + x) * a.ds[4 * l + 3];
   return a.det[l * 7 + k][off];
 }
+// 4 consecutive channels (channel-last bands, channel stride 1)
+__device__ __forceinline__ f32x4 idwt_coef4(const IdwtArgs& a, int l, int k, int b, int c,
+                                            int z, int y, int x) {
+  const int64_t Wl = (int64_t)a.w << l;
+  const int64_t off = b * a.ds[4 * l] + c + z * a.ds[4 * l + 2] + ((int64_t)y * Wl + x) * a.ds[4 * l + 3];
+  return *reinterpret_cast<const f32x4*>(a.det[l * 7 + k] + off);
+}
+
+// the 8 unscaled outputs of the finest cube (z1, y1, x1) from the coarsest LL at its ancestor:
+// slot n = sub-position (sz, sy, sx) = (n >> 2, n >> 1 & 1, n & 1)
+template <typename T, typename Coef>
+__device__ __forceinline__ void idwt_cube(T (&v)[8], T ll, int L, int z1, int y1, int x1,
+                                          Coef coef) {
+  v[0] = haar_ll_walk(ll, L, z1, y1, x1, coef);
+#pragma unroll
+  for (int k = 1; k < 8; ++k) v[k] = coef(L - 1, k - 1, z1, y1, x1);
+  haar_butterfly(v);
+}
 
 // CL: write a channel-last output (the decoder's concat buffer kept channels_last_3d) -- the
 // LDS image is then [2][2][2*w1][CB+1] (channels innermost, padded) and phase 2 writes each
@@ -152,40 +169,12 @@ __global__ __launch_bounds__(256) void idwt3d_haar_kernel(IdwtArgs a) {
     const int c = c0 + cl;
     // coarsest LL (NCDHW, contiguous spatial)
     const int zc = z1 >> (L - 1), yc = y1 >> (L - 1), xc = x1 >> (L - 1);
-    float ll = a.ll[b * a.ll_bstride + (int64_t)c * a.ll_cs +
-                    (((int64_t)zc * a.h + yc) * a.w + xc) * a.ll_ps];
-    // levels 0..L-2 produce the LL of the next level at the ancestor of (z1,y1,x1)
-    for (int l = 0; l < L - 1; ++l) {
-      const int sh = L - 1 - l;             // ancestor at level l is (z1,y1,x1) >> sh
-      const int zl = z1 >> sh, yl = y1 >> sh, xl = x1 >> sh;
-      const int sz = (z1 >> (sh - 1)) & 1, sy = (y1 >> (sh - 1)) & 1, sx = (x1 >> (sh - 1)) & 1;
-      float acc = ll;
-#pragma unroll
-      for (int k = 1; k < 8; ++k) {
-        const int bd = (k >> 2) & 1, bh = (k >> 1) & 1, bw = k & 1;
-        const int neg = (bd & sz) ^ (bh & sy) ^ (bw & sx);
-        const float cv = idwt_coef(a, l, k - 1, b, c, zl, yl, xl);
-        acc += neg ? -cv : cv;
-      }
-      ll = acc * kHaar3;
-    }
-    // finest level: all 8 outputs of the cube via inverse butterflies
+    const float ll = a.ll[b * a.ll_bstride + (int64_t)c * a.ll_cs +
+                          (((int64_t)zc * a.h + yc) * a.w + xc) * a.ll_ps];
     float v[8];
-    v[0] = ll;
-#pragma unroll
-    for (int k = 1; k < 8; ++k) v[k] = idwt_coef(a, L - 1, k - 1, b, c, z1, y1, x1);
-#pragma unroll
-    for (int bit = 1; bit < 8; bit <<= 1) {
-#pragma unroll
-      for (int n = 0; n < 8; ++n) {
-        if (!(n & bit)) {
-          const float s0 = v[n], s1 = v[n | bit];
-          v[n] = s0 + s1;
-          v[n | bit] = s0 - s1;
-        }
-      }
-    }
-    // slot n now holds sub-position (sz,sy,sx) = (n>>2, n>>1 & 1, n & 1)
+    idwt_cube(v, ll, L, z1, y1, x1, [&](int l, int k, int z, int y, int x) {
+      return idwt_coef(a, l, k, b, c, z, y, x);
+    });
 #pragma unroll
     for (int n = 0; n < 8; ++n) {
       const int sz = n >> 2, sy = (n >> 1) & 1, sx = n & 1;
@@ -246,44 +235,13 @@ __global__ __launch_bounds__(256) void idwt3d_haar_cl4_kernel(IdwtArgs a, int64_
   r /= (uint32_t)h1;
   const int z1 = (int)(r % (uint32_t)d1);
   const int b = (int)(r / (uint32_t)d1);
-  auto coef4 = [&](int l, int k, int z, int y, int x) {
-    const int64_t Wl = (int64_t)a.w << l;
-    const int64_t off = b * a.ds[4 * l] + c + z * a.ds[4 * l + 2] + ((int64_t)y * Wl + x) * a.ds[4 * l + 3];
-    return *reinterpret_cast<const f32x4*>(a.det[l * 7 + k] + off);
-  };
   const int zc = z1 >> (L - 1), yc = y1 >> (L - 1), xc = x1 >> (L - 1);
-  f32x4 ll = *reinterpret_cast<const f32x4*>(
+  const f32x4 ll = *reinterpret_cast<const f32x4*>(
       a.ll + b * a.ll_bstride + c + (((int64_t)zc * a.h + yc) * a.w + xc) * a.ll_ps);
-  for (int l = 0; l < L - 1; ++l) {
-    const int sh = L - 1 - l;
-    const int zl = z1 >> sh, yl = y1 >> sh, xl = x1 >> sh;
-    const int sz = (z1 >> (sh - 1)) & 1, sy = (y1 >> (sh - 1)) & 1, sx = (x1 >> (sh - 1)) & 1;
-    f32x4 cv[7];
-#pragma unroll
-    for (int k = 1; k < 8; ++k) cv[k - 1] = coef4(l, k - 1, zl, yl, xl);
-    f32x4 acc = ll;
-#pragma unroll
-    for (int k = 1; k < 8; ++k) {
-      const int neg = (((k >> 2) & 1) & sz) ^ (((k >> 1) & 1) & sy) ^ ((k & 1) & sx);
-      acc = neg ? acc - cv[k - 1] : acc + cv[k - 1];
-    }
-    ll = acc * kHaar3;
-  }
   f32x4 v[8];
-  v[0] = ll;
-#pragma unroll
-  for (int k = 1; k < 8; ++k) v[k] = coef4(L - 1, k - 1, z1, y1, x1);
-#pragma unroll
-  for (int bit = 1; bit < 8; bit <<= 1) {
-#pragma unroll
-    for (int n = 0; n < 8; ++n) {
-      if (!(n & bit)) {
-        const f32x4 s0 = v[n], s1 = v[n | bit];
-        v[n] = s0 + s1;
-        v[n | bit] = s0 - s1;
-      }
-    }
-  }
+  idwt_cube(v, ll, L, z1, y1, x1, [&](int l, int k, int z, int y, int x) {
+    return idwt_coef4(a, l, k, b, c, z, y, x);
+  });
   const int Wo = 2 * w1, Ho = 2 * h1;
   float* ob = a.out + b * a.out_bstride + c;
   if (CAT) {  // torch.cat((out, skip), 1): the same 4 channels of the skip, C further
@@ -326,14 +284,12 @@ __global__ __launch_bounds__(256) void idwt3d_haar_nc4_kernel(IdwtArgs a) {
   const int L = a.levels;
   const int w1 = a.w << (L - 1), h1 = a.h << (L - 1), d1 = a.d << (L - 1);
   const int Wo = 2 * w1, Ho = 2 * h1, Do = 2 * d1, WP = Wo + 2, LP = w1 + 1;
-  // 1-D grid of (row, channel block) with the channel blocks of a row adjacent and every XCD
-  // given a contiguous run: the blocks of one row read disjoint channel slices of the same
-  // channel-last detail lines, which now meet in one XCD's L2 (dealt round-robin over the XCDs,
-  // each block's 64-B slices pulled every 192-B position line again: 1.44x the algorithmic
-  // bytes)
+  // 1-D grid of (row, channel block), the channel blocks of a row adjacent, in XCD-contiguous
+  // order: the blocks of one row read disjoint channel slices of the same channel-last detail
+  // lines, which meet in one XCD's L2 (dealt round-robin, each block's 64-B slices pulled every
+  // 192-B position line again: 1.44x the algorithmic bytes)
   const int ncb = (a.C + a.CB - 1) / a.CB;
-  const int nb = gridDim.x, xcd = blockIdx.x & 7, q8 = nb >> 3, r8 = nb & 7;
-  const int lb = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
+  const int lb = xcd_block_id();
   int row = lb / ncb;
   const int y1 = row % h1;
   row /= h1;
@@ -354,44 +310,13 @@ __global__ __launch_bounds__(256) void idwt3d_haar_nc4_kernel(IdwtArgs a) {
   for (int item = threadIdx.x; item < CB4 * w1; item += blockDim.x) {
     const int q = item % CB4, x1 = item / CB4;
     const int cl = 4 * q, c = c0 + cl;
-    auto coef4 = [&](int l, int k, int z, int y, int x) {
-      const int64_t Wl = (int64_t)a.w << l;
-      const int64_t off = b * a.ds[4 * l] + c + z * a.ds[4 * l + 2] + ((int64_t)y * Wl + x) * a.ds[4 * l + 3];
-      return *reinterpret_cast<const f32x4*>(a.det[l * 7 + k] + off);
-    };
     const int xc = x1 >> (L - 1);
-    f32x4 ll = f32x4{lds_ll[cl * LP + xc], lds_ll[(cl + 1) * LP + xc], lds_ll[(cl + 2) * LP + xc],
-                     lds_ll[(cl + 3) * LP + xc]};
-    for (int l = 0; l < L - 1; ++l) {
-      const int sh = L - 1 - l;
-      const int zl = z1 >> sh, yl = y1 >> sh, xl = x1 >> sh;
-      const int sz = (z1 >> (sh - 1)) & 1, sy = (y1 >> (sh - 1)) & 1, sx = (x1 >> (sh - 1)) & 1;
-      f32x4 cv[7];
-#pragma unroll
-      for (int k = 1; k < 8; ++k) cv[k - 1] = coef4(l, k - 1, zl, yl, xl);
-      f32x4 acc = ll;
-#pragma unroll
-      for (int k = 1; k < 8; ++k) {
-        const int neg = (((k >> 2) & 1) & sz) ^ (((k >> 1) & 1) & sy) ^ ((k & 1) & sx);
-        acc = neg ? acc - cv[k - 1] : acc + cv[k - 1];
-      }
-      ll = acc * kHaar3;
-    }
+    const f32x4 ll = f32x4{lds_ll[cl * LP + xc], lds_ll[(cl + 1) * LP + xc],
+                           lds_ll[(cl + 2) * LP + xc], lds_ll[(cl + 3) * LP + xc]};
     f32x4 v[8];
-    v[0] = ll;
-#pragma unroll
-    for (int k = 1; k < 8; ++k) v[k] = coef4(L - 1, k - 1, z1, y1, x1);
-#pragma unroll
-    for (int bit = 1; bit < 8; bit <<= 1) {
-#pragma unroll
-      for (int n = 0; n < 8; ++n) {
-        if (!(n & bit)) {
-          const f32x4 s0 = v[n], s1 = v[n | bit];
-          v[n] = s0 + s1;
-          v[n | bit] = s0 - s1;
-        }
-      }
-    }
+    idwt_cube(v, ll, L, z1, y1, x1, [&](int l, int k, int z, int y, int x) {
+      return idwt_coef4(a, l, k, b, c, z, y, x);
+    });
     // slot n = (sz, sy, sx); the sx pair is adjacent in a row: one 8-B store per channel
 #pragma unroll
     for (int r = 0; r < 4; ++r) {

@@ -59,12 +59,9 @@ __global__ __launch_bounds__(512) void dwconv_ln_gelu_kernel(
   const int HP = Hd + 4;
   const int nchunk = Hd >> 2;
   const int ntx = (W + TW - 1) / TW, nty = (H + R - 1) / R;
-  // XCD-aware tile order: blocks b and b+8 share an XCD (round-robin dispatch), so give each
-  // XCD a contiguous run of (z, y, x) tiles -- neighbouring tiles re-read the same input rows
-  // and now find them in that XCD's L2 (bijective for any grid size; T1 of the HIP guide).
-  const int nb = gridDim.x;
-  const int xcd = blockIdx.x & 7, q8 = nb >> 3, r8 = nb & 7;
-  int t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
+  // XCD-contiguous (z, y, x) tile order: neighbouring tiles re-read the same input rows and
+  // find them in their XCD's L2
+  int t = xcd_block_id();
   const int xt = t % ntx;
   t /= ntx;
   const int yt = t % nty;
@@ -254,9 +251,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // XCD-contiguous tile order, channel chunk fastest, then x: the ncc workgroups that split
   // one spatial tile's Hd-wide rows run together (whole rows leave DRAM together), and
   // neighbouring tiles, which share halo rows, run on the same XCD and meet in its L2
-  const int nb = gridDim.x;
-  const int xcd = blockIdx.x & 7, q8 = nb >> 3, r8 = nb & 7;
-  int t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
+  int t = xcd_block_id();
   const int cc = t % ncc;
   t /= ncc;
   const int xt = t % ntx;

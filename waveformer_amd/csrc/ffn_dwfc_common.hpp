@@ -129,18 +129,15 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* p, int by
 }
 
 // ---- the workgroup's tile: (y0, x0) corner of its TY x TX tile, z segment [z0, z1) of ZS
-// planes, sample b.  XCD-contiguous order: workgroups i and i + 8 share an XCD (round-robin
-// dispatch), so each XCD gets a contiguous run of (z, y, x) tiles -- neighbouring tiles share
-// halo rows and meet in that XCD's L2 (bijective for any grid size).
+// planes, sample b.  XCD-contiguous order (xcd_block_id): each XCD gets a contiguous run of
+// (z, y, x) tiles -- neighbouring tiles share halo rows and meet in that XCD's L2.
 struct DwFcTile {
   int b, x0, y0, z0, z1;
 };
 template <int TY, int TX>
 __device__ __forceinline__ DwFcTile dwfc_tile(const DwFcArgs& a) {
   const int ntx = (a.W + TX - 1) / TX, nty = (a.H + TY - 1) / TY, nzs = (a.D + a.ZS - 1) / a.ZS;
-  const int nb = gridDim.x;
-  const int xcd = blockIdx.x & 7, q8 = nb >> 3, r8 = nb & 7;
-  int t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
+  int t = xcd_block_id();
   const int xt = t % ntx;
   t /= ntx;
   const int yt = t % nty;

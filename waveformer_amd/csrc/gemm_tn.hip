@@ -50,10 +50,8 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(TnArgs g) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int l15 = lane & 15, g4 = lane >> 4;
   // 1-D grid: the ntn x ntk tiles of one m chunk read the same rows of a and b (column
-  // slices of them), so they run adjacent on one XCD (XCD-contiguous runs of the linear id)
-  // instead of being dealt round-robin over the XCDs' separate L2s
-  const int nb = gridDim.x, xcd = blockIdx.x & 7, q8 = nb >> 3, r8 = nb & 7;
-  const int lb = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
+  // slices of them), so they run adjacent on one XCD
+  const int lb = xcd_block_id();
   const int bx = lb % (g.ntn * g.ntk), by = lb / (g.ntn * g.ntk);
   const int tn = bx % g.ntn, tk = bx / g.ntn;
   const int n0 = tn * TN_T, k0 = tk * TN_T;

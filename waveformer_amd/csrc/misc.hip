@@ -4,6 +4,8 @@
 
 #include <algorithm>
 
+#include "haar.hpp"
+#include "interp.hpp"
 #include "kernels.hpp"
 #include "rowgroup.hpp"
 
@@ -198,7 +200,7 @@ __global__ __launch_bounds__(256) void patch_embed_ll_kernel(
       c[n] = (val - ms.x) * ms.y * gw + gb;
     }
     const f32x4 s01 = c[0] + c[1], s23 = c[2] + c[3], s45 = c[4] + c[5], s67 = c[6] + c[7];
-    const f32x4 r = ((s01 + s23) + (s45 + s67)) * 0.35355339059327373f;
+    const f32x4 r = ((s01 + s23) + (s45 + s67)) * kHaar3;
     *reinterpret_cast<f32x4*>(ll + (lbase + lx) * COUT + 4 * q4) = r;
   }
 }
@@ -322,7 +324,7 @@ __global__ __launch_bounds__(256) void patch_embed_ll_mfma2_kernel(
     const f32x4 s45 = *reinterpret_cast<const f32x4*>(&pairs[2][o]);
     const f32x4 s67 = *reinterpret_cast<const f32x4*>(&pairs[3][o]);
     *reinterpret_cast<f32x4*>(ll + (lbase + lx) * COUT + 4 * q4) =
-        ((s01 + s23) + (s45 + s67)) * 0.35355339059327373f;
+        ((s01 + s23) + (s45 + s67)) * kHaar3;
   }
 }
 
@@ -591,6 +593,9 @@ struct MsfuseArgs {
   int B, C, D, H, W;
 };
 
+// src_index_rn with the identity spelled out for in == out (the formula gives the same values
+// there: scale = 1, src = o exactly); the adjoint takes the formula alone, 4 % faster without
+// the test
 __device__ __forceinline__ void lin_index(int o, int in, int out, int& i0, int& i1, float& l0,
                                           float& l1) {
   if (in == out) {
@@ -599,13 +604,7 @@ __device__ __forceinline__ void lin_index(int o, int in, int out, int& i0, int& 
     l1 = 0.f;
     return;
   }
-  const float scale = (float)in / (float)out;
-  float s = __fmul_rn(scale, (float)o + 0.5f) - 0.5f;
-  s = s < 0.f ? 0.f : s;
-  i0 = min((int)floorf(s), in - 1);
-  l1 = fminf(fmaxf(s - (float)i0, 0.f), 1.f);
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l0 = 1.f - l1;
+  src_index_rn(o, in, out, i0, i1, l0, l1);
 }
 
 template <int G, int V>
@@ -690,12 +689,9 @@ template <int G, int V, bool COAL = false>
 __global__ __launch_bounds__(256) void msfuse_row_kernel(MsfuseArgs a) {
   extern __shared__ __attribute__((aligned(16))) float R[];  // sum_s sw[s] * C [+ W * C: COAL]
   const int C = a.C, C4 = C >> 2;
-  // XCD-contiguous row order: the hardware deals consecutive workgroups round-robin over the
-  // 8 XCDs, which put neighbouring output rows -- which read the same 4 source rows per
-  // source -- on different XCDs, each fetching them into its own L2 (PMC: 1.25x the
-  // algorithmic bytes at stage 1).  Each XCD takes a contiguous run of rows instead.
-  const int nb = gridDim.x, xcd = blockIdx.x & 7, q8 = nb >> 3, r8 = nb & 7;
-  int r = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
+  // XCD-contiguous row order: neighbouring output rows read the same 4 source rows per source
+  // and meet in one XCD's L2 (dealt round-robin, PMC: 1.25x the algorithmic bytes at stage 1)
+  int r = xcd_block_id();
   const int y = r % a.H;
   r /= a.H;
   const int z = r % a.D;

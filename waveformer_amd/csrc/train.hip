@@ -15,6 +15,8 @@
 // autograd.py: dX = dY W on the streaming GEMM (gemm_rows.hip), dW = dY^T X on wf_gemm_tn
 // (gemm_tn.hip).  Everything here is fp32 VALU arithmetic: exact enough for
 // the fp32 reference's training and free of the split-bf16 bookkeeping.
+#include "haar.hpp"
+#include "interp.hpp"
 #include "kernels.hpp"
 
 namespace wf {
@@ -238,25 +240,9 @@ int64_t ln_parts(int64_t M) {
 // Haar adjoints.  Band k = (kd << 2) | (kh << 1) | kw  ('a' = 0, 'd' = 1; ptwt key order).
 // Analysis: band_k = sum_{i,j,l} x[2z+i][2y+j][2x+l] s(kd,i) s(kh,j) s(kw,l) / (2 sqrt 2),
 // s(0, .) = 1, s(1, i) = (i ? -1 : 1).  The matrix is orthogonal and symmetric up to the
-// index roles, so synthesis (= the analysis adjoint) uses the same signs.
+// index roles, so synthesis (= the analysis adjoint) uses the same signs: haar_butterfly and
+// kHaar3 (haar.hpp), the arithmetic of the dwt.hip kernels these two are the adjoints of.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void haar8(float (&v)[8]) {
-  // v indexed by (i<<2)|(j<<1)|l on input, by k on output (same butterfly both ways)
-  const float r = 0.35355339059327373f;  // 1 / (2 sqrt 2)
-#pragma unroll
-  for (int bit = 1; bit < 8; bit <<= 1) {
-#pragma unroll
-    for (int a = 0; a < 8; ++a) {
-      if (a & bit) continue;
-      const float p = v[a], q = v[a | bit];
-      v[a] = p + q;
-      v[a | bit] = p - q;
-    }
-  }
-#pragma unroll
-  for (int a = 0; a < 8; ++a) v[a] *= r;
-}
-
 struct BandPtrs {
   const float* p[8];
   int64_t s[8][5];  // (b, z, y, x, c) element strides
@@ -284,12 +270,12 @@ __global__ __launch_bounds__(256) void dwt_bwd_cl_kernel(BandPtrs bp, float* __r
                    c * bp.s[k][4]]
                : 0.f;
     }
-    haar8(v);
+    haar_butterfly(v);
     const int64_t H2 = 2 * h, W2 = 2 * w;
 #pragma unroll
     for (int a = 0; a < 8; ++a) {
       const int64_t zz = 2 * z + (a >> 2), yy = 2 * y + ((a >> 1) & 1), xx = 2 * x + (a & 1);
-      dx[((((int64_t)b * 2 * d + zz) * H2 + yy) * W2 + xx) * C + c] = v[a];
+      dx[((((int64_t)b * 2 * d + zz) * H2 + yy) * W2 + xx) * C + c] = v[a] * kHaar3;
     }
   }
 }
@@ -323,11 +309,11 @@ __global__ __launch_bounds__(256) void haar_analysis_ncdhw_kernel(
       const int64_t zz = 2 * z + (a >> 2), yy = 2 * y + ((a >> 1) & 1), xx = 2 * x + (a & 1);
       v[a] = src[zz * HW2 + yy * W2 + xx];
     }
-    haar8(v);
-    ll[i] = v[0];
+    haar_butterfly(v);
+    ll[i] = v[0] * kHaar3;
     const int64_t o = b * det.s[0] + c * det.s[1] + z * det.s[2] + y * det.s[3] + x * det.s[4];
 #pragma unroll
-    for (int k = 1; k < 8; ++k) det.p[k - 1][o] = v[k];
+    for (int k = 1; k < 8; ++k) det.p[k - 1][o] = v[k] * kHaar3;
   }
 }
 
@@ -589,21 +575,15 @@ __global__ __launch_bounds__(256) void rel_pos_bias_bwd_kernel(const float* __re
 }
 
 // ------------------------------------------------------------------------------------------
-// trilinear (align_corners=False) adjoint along one axis: in (outer, Lout, inner) ->
-// out (outer, Lin, inner), out[o][i][n] = sum_p w(p -> i) in[o][p][n] (gather form)
+// trilinear adjoint along one axis: in (outer, Lout, inner) -> out (outer, Lin, inner),
+// out[o][i][n] = sum_p w(p -> i) in[o][p][n] (gather form).  align_corners=False: w is the
+// multi-scale fuse's, by the fuse's own function (src_index_rn, interp.hpp).
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void lin_src(int p, int in, int out, int& i0, int& i1, float& l0,
-                                        float& l1) {
-  const float scale = (float)in / (float)out;
-  float s = __fmul_rn(scale, (float)p + 0.5f) - 0.5f;
-  s = s < 0.f ? 0.f : s;
-  i0 = min((int)floorf(s), in - 1);
-  l1 = fminf(fmaxf(s - (float)i0, 0.f), 1.f);
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l0 = 1.f - l1;
-}
-
-// align_corners=True: src = p * (in - 1) / (out - 1) (PyTorch's area_pixel_compute_scale)
+// align_corners=True: src = p * (in - 1) / (out - 1) (PyTorch's area_pixel_compute_scale), the
+// decoder's up-sampling (upsample.hip).  Not interp.hpp's src_index: here the compiler
+// contracts s - i0 with the product into one FMA, which is negative where the rounded product
+// lands on an integer from below; the clamp makes that 0, src_index has none, and the results
+// differ in the last bit (6 -> 24)
 __device__ __forceinline__ void lin_src_ac(int p, int in, int out, int& i0, int& i1, float& l0,
                                            float& l1) {
   const float scale = out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
@@ -642,7 +622,7 @@ __global__ __launch_bounds__(256) void interp_adjoint_kernel(
       int i0, i1;
       float l0, l1;
       if (AC) lin_src_ac(p, Lin, Lout, i0, i1, l0, l1);
-      else lin_src(p, Lin, Lout, i0, i1, l0, l1);
+      else src_index_rn(p, Lin, Lout, i0, i1, l0, l1);
       float wgt = (i0 == i ? l0 : 0.f) + (i1 == i ? l1 : 0.f);
       if (wgt != 0.f) acc = fmaf(wgt, src[(int64_t)p * inner], acc);
     }

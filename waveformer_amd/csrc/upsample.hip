@@ -10,43 +10,9 @@
 // (the source is 8-64x smaller than the output), the output is written once (HBM roofline).
 #include <algorithm>
 
-#include "wf_common.hpp"
+#include "interp.hpp"
 
 namespace wf {
-
-struct Src1 {
-  int i0, i1;
-  float l0, l1;
-};
-
-// src_index with the axis' scale precomputed (scale = src_scale(in, out, ac), the same fp32
-// division): the fused up-sample + conv forms thousands of indices per plane
-__device__ __forceinline__ Src1 src_index_s(int dst, int in, float scale, bool ac) {
-  Src1 s;
-  const float r = ac ? scale * (float)dst : fmaxf(scale * ((float)dst + 0.5f) - 0.5f, 0.f);
-  s.i0 = (int)r;
-  s.i1 = s.i0 + (s.i0 < in - 1 ? 1 : 0);
-  s.l1 = r - (float)s.i0;
-  s.l0 = 1.f - s.l1;
-  return s;
-}
-
-__device__ __forceinline__ Src1 src_index(int dst, int in, int out, bool ac) {
-  Src1 s;
-  float r;
-  if (ac) {
-    const float scale = out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
-    r = scale * (float)dst;
-  } else {
-    const float scale = (float)in / (float)out;
-    r = fmaxf(scale * ((float)dst + 0.5f) - 0.5f, 0.f);
-  }
-  s.i0 = (int)r;
-  s.i1 = s.i0 + (s.i0 < in - 1 ? 1 : 0);
-  s.l1 = r - (float)s.i0;
-  s.l0 = 1.f - s.l1;
-  return s;
-}
 
 // l0 a + l1 b with the contraction spelled out (one multiply, one FMA): the fused
 // up-sample + depthwise conv forms the same values as upsample_cl_lds_kernel bit for bit only if
@@ -64,11 +30,9 @@ __global__ __launch_bounds__(256) void upsample_cl_kernel(const float* __restric
                                                           int h, int w, int D, int H, int W,
                                                           int ac) {
   const int C4 = C >> 2;
-  // XCD-contiguous row order (workgroups are dealt round-robin over the 8 XCDs): the
-  // neighbouring output rows that read the same source rows run on one XCD and meet in its L2
-  const int nb = gridDim.x, xcd = blockIdx.x & 7, q8 = nb >> 3, r8 = nb & 7;
-  const int row = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) +
-                  (blockIdx.x >> 3);  // (b * D + z) * H + y
+  // XCD-contiguous row order: the neighbouring output rows that read the same source rows
+  // meet in one XCD's L2
+  const int row = xcd_block_id();  // (b * D + z) * H + y
   const int y = row % H, bz = row / H;
   const int z = bz % D, b = bz / D;
   const Src1 sz = src_index(z, d, D, ac), sy = src_index(y, h, H, ac);
@@ -183,9 +147,7 @@ __global__ __launch_bounds__(256) void upsample_dwconv3d_kernel(
 
   const int ncc = C / CH, ntx = (W + TX - 1) / TX, nty = (H + TY - 1) / TY;
   const int nzs = (D + ZS - 1) / ZS;
-  const int nb = gridDim.x;  // XCD-contiguous tile order, as dwconv3d_kernel
-  const int xcd = blockIdx.x & 7, q8 = nb >> 3, r8 = nb & 7;
-  int t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
+  int t = xcd_block_id();  // XCD-contiguous tile order, as dwconv3d_kernel
   const int cc = t % ncc;
   t /= ncc;
   const int xt = t % ntx;
@@ -385,9 +347,7 @@ __global__ __launch_bounds__(256) void upsample_cl_lds_kernel(const float* __res
                                                               int W, int ac) {
   extern __shared__ __attribute__((aligned(16))) float rowbuf[];  // [w][C]
   const int C4 = C >> 2;
-  const int nb = gridDim.x, xcd = blockIdx.x & 7, q8 = nb >> 3, r8 = nb & 7;
-  const int row = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) +
-                  (blockIdx.x >> 3);  // (b * D + z) * H + y
+  const int row = xcd_block_id();  // (b * D + z) * H + y, XCD-contiguous
   const int y = row % H, bz = row / H;
   const int z = bz % D, b = bz / D;
   const Src1 sz = src_index(z, d, D, ac), sy = src_index(y, h, H, ac);
@@ -473,26 +433,16 @@ extern "C" int wf_upsample_dwconv3d_stats_cl(const float* in, const float* w, co
   WF_REQUIRE_PTR(stats_acc);
   // every tile's source columns / rows (haloed, both blend neighbours) must fit the Q staging
   const bool ac = align_corners != 0;
-  auto scale = [&](int64_t n_in, int64_t n_out) -> float {  // src_index's fp32 scale
-    if (ac) return n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f;
-    return (float)n_in / (float)n_out;
-  };
-  auto sidx =[&](int64_t dst, int64_t n_in, float sc) -> Src1 {  // src_index_s on the host
-    Src1 s;
-    const float r = ac ? sc * (float)dst : std::max(sc * ((float)dst + 0.5f) - 0.5f, 0.f);
-    s.i0 = (int)r;
-    s.i1 = s.i0 + (s.i0 < n_in - 1 ? 1 : 0);
-    return s;
-  };
-  const float scz = scale(d, D), scy = scale(h, H), scx = scale(wd, W);
+  const float scz = src_scale((int)d, (int)D, ac), scy = src_scale((int)h, (int)H, ac),
+              scx = src_scale((int)wd, (int)W, ac);
   for (int64_t x0 = 0; x0 < W; x0 += UD_TX) {
-    const int lo = sidx(std::max<int64_t>(x0 - 1, 0), wd, scx).i0;
-    const int hi = sidx(std::min<int64_t>(x0 + UD_TX, W - 1), wd, scx).i1;
+    const int lo = src_index_s((int)std::max<int64_t>(x0 - 1, 0), (int)wd, scx, ac).i0;
+    const int hi = src_index_s((int)std::min<int64_t>(x0 + UD_TX, W - 1), (int)wd, scx, ac).i1;
     WF_REQUIRE(hi - lo + 1 <= UD_SX, "up-sampling factor along x below 2 (source span > 12)");
   }
   for (int64_t y0 = 0; y0 < H; y0 += UD_TY) {
-    const int lo = sidx(std::max<int64_t>(y0 - 1, 0), h, scy).i0;
-    const int hi = sidx(std::min<int64_t>(y0 + UD_TY, H - 1), h, scy).i1;
+    const int lo = src_index_s((int)std::max<int64_t>(y0 - 1, 0), (int)h, scy, ac).i0;
+    const int hi = src_index_s((int)std::min<int64_t>(y0 + UD_TY, H - 1), (int)h, scy, ac).i1;
     WF_REQUIRE(hi - lo + 1 <= UD_SY, "up-sampling factor along y below 2 (source span > 7)");
   }
   hipStream_t s = (hipStream_t)stream;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <type_traits>
 
 #include "../../include/waveformer_hip.h"
 
@@ -156,6 +157,24 @@ __device__ __forceinline__ float xsum16(float v) {
 __device__ __forceinline__ float xsum32(float v) {
   const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), true, false);
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+
+// ---------------------------------------------------------------------------------------
+// XCD-contiguous workgroup order
+// ---------------------------------------------------------------------------------------
+// The workgroups of a 1-D grid are dealt round-robin over the 8 XCDs (linear ids L and L + 8
+// share an XCD), each XCD with an L2 of its own: neighbours in L, which usually read the same
+// rows, would each fetch them into another L2.  The logical id returned here is the (L / 8)-th
+// slot of group L % 8 in a split of the grid into 8 contiguous runs (the first gridDim.x % 8
+// runs one longer), so consecutive logical ids share an XCD; bijective for any grid size.  A
+// kernel decodes its tile from this id instead of blockIdx.x.  A speed choice only: no result
+// depends on the placement.  I: the integer type of the arithmetic (attention.hip decodes in
+// 64 bits); L / 8 is a logical shift in either width.
+template <typename I = int>
+__device__ __forceinline__ I xcd_block_id() {
+  const I L = blockIdx.x, nb = gridDim.x;
+  const I xcd = L & 7, q8 = nb >> 3, r8 = nb & 7;
+  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (I)((std::make_unsigned_t<I>)L >> 3);
 }
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
