@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define WF_ABI_VERSION 23
+#define WF_ABI_VERSION 24
 
 enum { WF_PREC_BF16 = 0, WF_PREC_BF16X3 = 1, WF_PREC_FP16 = 2 };
 
@@ -810,6 +810,80 @@ int wf_surface_hist(const uint8_t* border_a, const uint32_t* d2_b, const uint8_t
 int wf_hist_order_stats(const uint32_t* hist, int64_t G, int64_t group, int64_t nbins,
                         int64_t q_num, int64_t q_den, const int64_t* offsets, int64_t nranks,
                         int64_t* out, void* stream);
+
+/* ======================================================================================
+ * Preprocessing (ABI 24): the per-case array transform of 2_preprocessing_mri.py
+ * (MultiModalityPreprocessor.run_case_npy, light_training/preprocessing): crop to the
+ * hole-filled nonzero mask, z-score every modality, mark the outside in the segmentation, and
+ * pick the sampled foreground voxels by rank.  Volumes are (D, H, W) with D*H*W < 2^31 and
+ * W <= 2^20.  Integer atomics only; the fp64 moments are summed in a fixed order, so every
+ * output is bitwise repeatable.  Workspaces are the caller's.
+ * ====================================================================================== */
+
+/* create_nonzero_mask without the fill (cropping.py:16-19): mask[v] = OR over c of
+ * data[c][v] != 0 with numpy's comparison -- -0.0 is zero, a denormal and a NaN are not (the
+ * bits are tested, not a float compare that flush-to-zero would bend).  data (C, D, H, W)
+ * fp32, 1 <= C <= 64; mask (D, H, W) uint8 of 0 / 1.                                        */
+int wf_nonzero_mask(const float* data, int64_t C, int64_t D, int64_t H, int64_t W,
+                    uint8_t* mask, void* stream);
+
+/* scipy.ndimage.binary_fill_holes with its default structure (cropping.py:20): filled = every
+ * voxel that is not background joined to the array border by a 6-connected background path.
+ * mask, filled: (D, H, W) uint8, non-zero = set in, 0 / 1 out; they may be the same buffer.
+ * bbox: 8 device int64 {z0, z1, y0, y1, x0, x1, count, 0}: the half-open bounding box of the
+ * filled mask (acvl_utils' get_bbox_from_mask) and its voxel count, all 0 for an empty mask.
+ * rounds (host, may be NULL): the number of sweep rounds that marked a voxel.
+ * Line-sweep launches along x, y and z carry the outside state; a launch never reads what
+ * another workgroup writes in it, and no device loop waits on another workgroup.  The call
+ * SYNCHRONISES the stream after every batch of 8 rounds to read 8 "changed" words, so it cannot
+ * be captured into a graph.  workspace: wf_fill_holes_workspace_bytes() bytes, 8-byte aligned. */
+int64_t wf_fill_holes_workspace_bytes(int64_t D, int64_t H, int64_t W);
+int wf_fill_holes(const uint8_t* mask, int64_t D, int64_t H, int64_t W, uint8_t* filled,
+                  int64_t* bbox, void* workspace, int64_t workspace_bytes, int64_t* rounds,
+                  void* stream);
+
+/* Mean and population standard deviation of every channel of data (C, D, H, W) fp32 over the
+ * half-open box (6 host int64 {z0, z1, y0, y1, x0, x1}): stats (C, 2) device fp64 {mean, std}
+ * (image.mean(), image.std() of default_normalization_schemes.py:47-48, in fp64).  Sums of
+ * (x - first voxel) and its square in fp64 per workgroup, added up in a fixed order by a second
+ * kernel.  16-byte loads when x0, the box width, W and D*H*W are multiples of 4 and data is
+ * 16-byte aligned, scalar loads otherwise.  workspace: wf_box_moments_workspace_bytes(C, d, h,
+ * w) bytes for a box of d x h x w.                                                           */
+int64_t wf_box_moments_workspace_bytes(int64_t C, int64_t d, int64_t h, int64_t w);
+int wf_box_moments(const float* data, int64_t C, int64_t D, int64_t H, int64_t W,
+                   const int64_t* box, double* stats, void* workspace, int64_t workspace_bytes,
+                   void* stream);
+
+/* out (C, d, h, w) fp32 = data[:, box]; with stats (C, 2) fp64 {mean, std} also z-scored,
+ * (x - fp32(mean)) / max(fp32(std), 1e-8) in fp32 (ZScoreNormalization with
+ * use_mask_for_norm=False, :49); stats NULL copies.  out == data is allowed when the box is the
+ * whole volume.  The same 16-byte / scalar paths as wf_box_moments.                          */
+int wf_crop_normalize(const float* data, int64_t C, int64_t D, int64_t H, int64_t W,
+                      const int64_t* box, const double* stats, float* out, void* stream);
+
+/* The cropped segmentation of crop_to_nonzero (cropping.py:38-48): seg (D, H, W) int16 or NULL,
+ * filled (D, H, W) uint8.  out (d, h, w) int16: with a seg, seg[box] with `label` where seg == 0
+ * outside the filled mask; without, 0 inside the mask and `label` outside.  maxv: one device
+ * int, the largest value written (the reference stores int8 unless it exceeds 127).        */
+int wf_crop_seg(const int16_t* seg, const uint8_t* filled, int64_t D, int64_t H, int64_t W,
+                const int64_t* box, int label, int16_t* out, int* maxv, void* stream);
+
+/* Ranked selection: "the k-th voxel in C order whose label satisfies the predicate" -- what
+ * np.argwhere(seg == c)[ranks] and image[seg > 0][ranks] need (default_preprocessor.py:414-483)
+ * without materialising the argwhere.  labels: S int16.  mode WF_SELECT_EQ: label == value,
+ * WF_SELECT_GT: label > value.  wf_select_scan counts the selected voxels per tile of 1024 and
+ * scans the counts into the workspace (wf_select_workspace_bytes(S) bytes, 8-byte aligned) and
+ * writes their number to *total (device int64).  wf_select_pick, with the same labels, mode,
+ * value and the scanned workspace, resolves nq device int64 ranks: coords (nq, 4) int64 rows
+ * (0, z, y, x) when not NULL, vals[q] = image[voxel] (image: D*H*W fp32) when not NULL.  A rank
+ * outside [0, total) gives a row of -1 and a NaN.                                            */
+enum { WF_SELECT_EQ = 0, WF_SELECT_GT = 1 };
+int64_t wf_select_workspace_bytes(int64_t S);
+int wf_select_scan(const int16_t* labels, int64_t S, int mode, int value, void* workspace,
+                   int64_t workspace_bytes, int64_t* total, void* stream);
+int wf_select_pick(const int16_t* labels, int64_t D, int64_t H, int64_t W, int mode, int value,
+                   const void* workspace, int64_t workspace_bytes, const int64_t* ranks,
+                   int64_t nq, int64_t* coords, const float* image, float* vals, void* stream);
 
 #ifdef __cplusplus
 }

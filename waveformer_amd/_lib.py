@@ -152,9 +152,20 @@ SIGNATURES = {
     "wf_surface_edt_sq": (_I, [_P, _I64, _I64, _I64, _I64, _P, _P, _P, _I64, _P]),
     "wf_surface_hist": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P]),
     "wf_hist_order_stats": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _P, _P]),
+    # preprocessing (nonzero crop, hole fill, z-score, ranked selection)
+    "wf_nonzero_mask": (_I, [_P, _I64, _I64, _I64, _I64, _P, _P]),
+    "wf_fill_holes_workspace_bytes": (_I64, [_I64, _I64, _I64]),
+    "wf_fill_holes": (_I, [_P, _I64, _I64, _I64, _P, _P, _P, _I64, _P, _P]),
+    "wf_box_moments_workspace_bytes": (_I64, [_I64, _I64, _I64, _I64]),
+    "wf_box_moments": (_I, [_P, _I64, _I64, _I64, _I64, _P, _P, _P, _I64, _P]),
+    "wf_crop_normalize": (_I, [_P, _I64, _I64, _I64, _I64, _P, _P, _P, _P]),
+    "wf_crop_seg": (_I, [_P, _P, _I64, _I64, _I64, _P, _I, _P, _P, _P]),
+    "wf_select_workspace_bytes": (_I64, [_I64]),
+    "wf_select_scan": (_I, [_P, _I64, _I, _I, _P, _I64, _P, _P]),
+    "wf_select_pick": (_I, [_P, _I64, _I64, _I64, _I, _I, _P, _I64, _P, _I64, _P, _P, _P, _P]),
 }
 
-ABI_VERSION = 23
+ABI_VERSION = 24
 _lock = threading.Lock()
 _lib = None
 _err = None

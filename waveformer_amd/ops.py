@@ -1924,3 +1924,173 @@ def hist_order_stats(hist: torch.Tensor, offsets: Sequence[int], q: Tuple[int, i
     _lib.call("wf_hist_order_stats", hist.data_ptr(), G, int(group), nbins, int(q[0]), int(q[1]),
               offs, len(offsets), out.data_ptr(), _stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------
+# preprocessing: nonzero mask, hole fill, box moments, crop, ranked selection
+# (waveformer_amd.preprocessing)
+# ------------------------------------------------------------------------------------------
+SELECT_EQ, SELECT_GT = 0, 1
+GUARD_BYTES = 256            # poison after a preprocessing workspace when guards are asked for
+_GUARD_VALUE = 0xA5
+
+
+def _workspace(nbytes: int, device, who: str, guard: bool = False) -> torch.Tensor:
+    """A caller-owned workspace of nbytes (a failed size query is an error), optionally followed
+    by GUARD_BYTES of 0xA5 that check_guard() verifies."""
+    if nbytes < 0:
+        raise RuntimeError(f"{who} failed: " + _lib.load().wf_last_error().decode(errors="replace"))
+    if guard:
+        ws = torch.empty((nbytes + GUARD_BYTES,), dtype=torch.uint8, device=device)
+        ws[nbytes:] = _GUARD_VALUE
+        return ws
+    return torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=device)
+
+
+def check_guard(ws: torch.Tensor, nbytes: int) -> bool:
+    """True if the guard bytes behind the first nbytes of a guarded workspace are untouched."""
+    return bool((ws[nbytes:] == _GUARD_VALUE).all().item())
+
+
+def _volume4(data: torch.Tensor, who: str) -> Tuple[int, int, int, int]:
+    _check(data, "data")
+    if data.dim() != 4:
+        raise ValueError(f"{who}: expected (C, D, H, W), got {tuple(data.shape)}")
+    return tuple(int(v) for v in data.shape)
+
+
+def _box(box: Sequence[Sequence[int]]):
+    flat = [int(v) for pair in box for v in pair]
+    if len(flat) != 6:
+        raise ValueError(f"box must be [[z0, z1], [y0, y1], [x0, x1]], got {box!r}")
+    return (ctypes.c_int64 * 6)(*flat), tuple(flat[2 * a + 1] - flat[2 * a] for a in range(3))
+
+
+def nonzero_mask(data: torch.Tensor) -> torch.Tensor:
+    """(D, H, W) uint8 mask of the voxels where any channel of data (C, D, H, W) fp32 is nonzero
+    as numpy compares: -0.0 is zero, a denormal and a NaN are not (wf_nonzero_mask)."""
+    C, D, H, W = _volume4(data, "nonzero_mask")
+    mask = torch.empty((D, H, W), dtype=torch.uint8, device=data.device)
+    _lib.call("wf_nonzero_mask", data.data_ptr(), C, D, H, W, mask.data_ptr(), _stream())
+    return mask
+
+
+def fill_holes(mask: torch.Tensor, guard: bool = False
+               ) -> Tuple[torch.Tensor, torch.Tensor, int]:
+    """scipy.ndimage.binary_fill_holes (default structure) of a (D, H, W) uint8 mask
+    (wf_fill_holes).  Returns (filled uint8 0 / 1, bbox: 8 device int64 {z0, z1, y0, y1, x0, x1,
+    count, 0} of the filled mask, the number of sweep rounds that marked a voxel).  Synchronises
+    the stream.  guard: put guard bytes after the workspace and raise if they were written."""
+    _check(mask, "mask", dtype=torch.uint8)
+    if mask.dim() != 3:
+        raise ValueError(f"fill_holes: expected (D, H, W), got {tuple(mask.shape)}")
+    D, H, W = (int(v) for v in mask.shape)
+    nbytes = _lib.query("wf_fill_holes_workspace_bytes", D, H, W)
+    ws = _workspace(nbytes, mask.device, "wf_fill_holes_workspace_bytes", guard)
+    filled = torch.empty_like(mask)
+    bbox = torch.empty((8,), dtype=torch.int64, device=mask.device)
+    rounds = ctypes.c_int64(0)
+    _lib.call("wf_fill_holes", mask.data_ptr(), D, H, W, filled.data_ptr(), bbox.data_ptr(),
+              ws.data_ptr(), nbytes, ctypes.byref(rounds), _stream())
+    if guard and not check_guard(ws, nbytes):
+        raise RuntimeError("wf_fill_holes wrote past its workspace")
+    return filled, bbox, int(rounds.value)
+
+
+def box_moments(data: torch.Tensor, box: Sequence[Sequence[int]], guard: bool = False
+                ) -> torch.Tensor:
+    """(C, 2) fp64 {mean, population std} of every channel of data (C, D, H, W) fp32 over the
+    half-open box [[z0, z1], [y0, y1], [x0, x1]] (wf_box_moments): bitwise repeatable."""
+    C, D, H, W = _volume4(data, "box_moments")
+    cbox, size = _box(box)
+    nbytes = _lib.query("wf_box_moments_workspace_bytes", C, *size)
+    ws = _workspace(nbytes, data.device, "wf_box_moments_workspace_bytes", guard)
+    stats = torch.empty((C, 2), dtype=torch.float64, device=data.device)
+    _lib.call("wf_box_moments", data.data_ptr(), C, D, H, W, cbox, stats.data_ptr(),
+              ws.data_ptr(), nbytes, _stream())
+    if guard and not check_guard(ws, nbytes):
+        raise RuntimeError("wf_box_moments wrote past its workspace")
+    return stats
+
+
+def crop_normalize(data: torch.Tensor, box: Sequence[Sequence[int]],
+                   stats: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None
+                   ) -> torch.Tensor:
+    """data[:, box] as a new (C, d, h, w) fp32 tensor, z-scored with stats (C, 2) fp64
+    {mean, std} when given: (x - mean) / max(std, 1e-8) in fp32 (wf_crop_normalize).  out=data
+    normalises in place when the box is the whole volume."""
+    C, D, H, W = _volume4(data, "crop_normalize")
+    cbox, size = _box(box)
+    if stats is not None:
+        _check(stats, "stats", dtype=torch.float64)
+        if tuple(stats.shape) != (C, 2):
+            raise ValueError(f"crop_normalize: stats {tuple(stats.shape)} != {(C, 2)}")
+    if out is None:
+        out = torch.empty((C,) + size, dtype=torch.float32, device=data.device)
+    else:
+        _check(out, "out")
+        if tuple(out.shape) != (C,) + size:
+            raise ValueError(f"crop_normalize: out {tuple(out.shape)} != {(C,) + size}")
+    _lib.call("wf_crop_normalize", data.data_ptr(), C, D, H, W, cbox, _ptr(stats),
+              out.data_ptr(), _stream())
+    return out
+
+
+def crop_seg(seg: Optional[torch.Tensor], filled: torch.Tensor, box: Sequence[Sequence[int]],
+             label: int = -1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """crop_to_nonzero's segmentation (wf_crop_seg): seg (D, H, W) int16 or None and the filled
+    mask (D, H, W) uint8 -> ((d, h, w) int16, one device int32 holding its maximum)."""
+    _check(filled, "filled", dtype=torch.uint8)
+    if filled.dim() != 3:
+        raise ValueError(f"crop_seg: expected a (D, H, W) mask, got {tuple(filled.shape)}")
+    if seg is not None:
+        _check(seg, "seg", dtype=torch.int16)
+        if seg.shape != filled.shape:
+            raise ValueError(f"crop_seg: seg {tuple(seg.shape)} != mask {tuple(filled.shape)}")
+    cbox, size = _box(box)
+    out = torch.empty(size, dtype=torch.int16, device=filled.device)
+    maxv = torch.empty((1,), dtype=torch.int32, device=filled.device)
+    _lib.call("wf_crop_seg", _ptr(seg), filled.data_ptr(), *filled.shape, cbox, int(label),
+              out.data_ptr(), maxv.data_ptr(), _stream())
+    return out, maxv
+
+
+class Selection:
+    """The scanned tile counts of `labels <mode> value` over a (D, H, W) int16 label map
+    (wf_select_scan): `total` is one device int64, `pick` resolves ranks (wf_select_pick)."""
+
+    def __init__(self, labels: torch.Tensor, mode: int, value: int, guard: bool = False):
+        _check(labels, "labels", dtype=torch.int16)
+        if labels.dim() != 3:
+            raise ValueError(f"Selection: expected (D, H, W) labels, got {tuple(labels.shape)}")
+        self.labels, self.mode, self.value = labels, int(mode), int(value)
+        S = labels.numel()
+        self.nbytes = _lib.query("wf_select_workspace_bytes", S)
+        self.ws = _workspace(self.nbytes, labels.device, "wf_select_workspace_bytes", guard)
+        self.total = torch.empty((1,), dtype=torch.int64, device=labels.device)
+        _lib.call("wf_select_scan", labels.data_ptr(), S, self.mode, self.value,
+                  self.ws.data_ptr(), self.nbytes, self.total.data_ptr(), _stream())
+        if guard and not check_guard(self.ws, self.nbytes):
+            raise RuntimeError("wf_select_scan wrote past its workspace")
+
+    def pick(self, ranks: torch.Tensor, image: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """ranks: (nq,) device int64 of 0-based ranks in C order.  Without an image: (nq, 4)
+        int64 rows (0, z, y, x); with image (D, H, W) fp32: its (nq,) values there."""
+        _check(ranks, "ranks", dtype=torch.int64)
+        nq = ranks.numel()
+        D, H, W = (int(v) for v in self.labels.shape)
+        dev = self.labels.device
+        if image is None:
+            out = torch.empty((nq, 4), dtype=torch.int64, device=dev)
+            args = (out.data_ptr(), None, None)
+        else:
+            _check(image, "image")
+            if image.shape != self.labels.shape:
+                raise ValueError(f"pick: image {tuple(image.shape)} != labels "
+                                 f"{tuple(self.labels.shape)}")
+            out = torch.empty((nq,), dtype=torch.float32, device=dev)
+            args = (None, image.data_ptr(), out.data_ptr())
+        if nq:
+            _lib.call("wf_select_pick", self.labels.data_ptr(), D, H, W, self.mode, self.value,
+                      self.ws.data_ptr(), self.nbytes, ranks.data_ptr(), nq, *args, _stream())
+        return out
