@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define WF_ABI_VERSION 24
+#define WF_ABI_VERSION 25
 
 enum { WF_PREC_BF16 = 0, WF_PREC_BF16X3 = 1, WF_PREC_FP16 = 2 };
 
@@ -884,6 +884,80 @@ int wf_select_scan(const int16_t* labels, int64_t S, int mode, int value, void* 
 int wf_select_pick(const int16_t* labels, int64_t D, int64_t H, int64_t W, int mode, int value,
                    const void* workspace, int64_t workspace_bytes, const int64_t* ranks,
                    int64_t nq, int64_t* coords, const float* image, float* vals, void* stream);
+
+/* ======================================================================================
+ * Train-time augmentation (ABI 25): the kernels under waveformer_amd.augment, the device form
+ * of light_training/augment/train_augment.py (batchgenerators' SpatialTransform, GaussianBlur,
+ * BrightnessMultiplicative, ContrastAugmentation, SimulateLowResolution and Gamma transforms).
+ * Planes are (D, H, W) fp32 with D*H*W < 2^31; N planes lie back to back.  No launch reads what
+ * another workgroup writes in it, no device loop waits on another workgroup, and there are no
+ * float atomics: every output is bitwise repeatable.
+ * ====================================================================================== */
+
+/* The cubic B-spline prefilter of scipy.ndimage (pole sqrt(3) - 2, gain 6) along one axis
+ * (0 = D, 1 = H, 2 = W) of N planes, as a symmetric FIR of 18 taps on either side (the impulse
+ * response sqrt(3) pole^|k|, below 2^-30 of its centre after 16 samples).
+ * WF_SPLINE_MIRROR: scipy's `mirror` boundary, what map_coordinates(mode='constant') filters
+ * with; out has in's shape; an axis of length 1 is copied, as scipy leaves it alone.
+ * WF_SPLINE_EDGE: what zoom(mode='nearest', grid_mode=True) filters with: WF_SPLINE_PAD edge
+ * samples on either side (virtual: in is read clamped), mirrored beyond them; out is
+ * WF_SPLINE_PAD * 2 longer than in along the axis and keeps the padding.  in != out.        */
+enum { WF_SPLINE_MIRROR = 0, WF_SPLINE_EDGE = 1 };
+#define WF_SPLINE_PAD 12
+int wf_spline_prefilter_axis(const float* in, float* out, int64_t N, int64_t D, int64_t H,
+                             int64_t W, int axis, int mode, void* stream);
+
+/* scipy.ndimage.gaussian_filter1d along one axis of N planes (mode `reflect`): weights: radius +
+ * 1 host floats, the centre first (the kernel is symmetric), radius <= 20.  in != out.        */
+int wf_gauss_blur_axis(const float* in, float* out, int64_t N, int64_t D, int64_t H, int64_t W,
+                       int axis, const float* weights, int radius, void* stream);
+
+/* augment_spatial's interpolation for one sample.  matrix: 12 host doubles, row j (z, y, x of
+ * the input) {m0, m1, m2, t}: an output voxel o of the (oD, oH, oW) patch reads the input at
+ * sum_i (o_i - (on_i - 1) / 2) m_i + t, in fp64.  A point outside [0, n - 1] on any axis gives
+ * cval.  coef (C, D, H, W): the channels after wf_spline_prefilter_axis(MIRROR) on all axes;
+ * out (C, oD, oH, oW) = map_coordinates(order=3, mode='constant', cval=0): 64 taps, indices
+ * mirrored.  seg (D, H, W) fp32 labels; out_seg (oD, oH, oW) = interpolate_img(order=1,
+ * cval=-1, is_seg=True): the weights of the eight trilinear taps are summed per distinct label
+ * in fp64 and the largest label whose sum is >= 0.5 wins, else 0.  Either pair may be NULL.  */
+int wf_affine_sample(const float* coef, const float* seg, const double* matrix, int64_t C,
+                     int64_t D, int64_t H, int64_t W, int64_t oD, int64_t oH, int64_t oW,
+                     float* out, float* out_seg, void* stream);
+
+/* scipy.ndimage.zoom(order=0, mode='nearest', grid_mode=True) of N planes (D, H, W) to
+ * (oD, oH, oW): skimage.transform.resize(order=0, mode='edge', anti_aliasing=False).  Exact. */
+int wf_zoom_nearest(const float* in, int64_t N, int64_t D, int64_t H, int64_t W, int64_t oD,
+                    int64_t oH, int64_t oW, float* out, void* stream);
+
+/* zoom(order=3, mode='nearest', grid_mode=True) of N planes (D, H, W) to (oD, oH, oW): coef is
+ * the padded (N, D + 24, H + 24, W + 24) output of wf_spline_prefilter_axis(EDGE) on all axes,
+ * sampled at (o + 0.5) n / on - 0.5 + 12.                                                    */
+int wf_zoom_cubic(const float* coef, int64_t N, int64_t D, int64_t H, int64_t W, int64_t oD,
+                  int64_t oH, int64_t oW, float* out, void* stream);
+
+/* One intensity step on N planes of S voxels, in place, and the statistics of the result.
+ * params (N, 4) device fp64 {drawn (0 / 1), value, sign (+1 / -1), 0}: a plane that is not
+ * drawn is not written.  stats_* (N, 4) device fp64 {mean, population std, min, max}.
+ *   WF_AUG_NONE           nothing (statistics only; params may be NULL)
+ *   WF_AUG_SCALE          x * value
+ *   WF_AUG_CONTRAST       (x - mean) value + mean clipped to [min, max], from stats_a
+ *   WF_AUG_GAMMA_POW      y = sign x; ((y - min_y) / (range + 1e-7)) ^ value * range + min_y, the
+ *                         statistics of y derived from stats_a (those of x); writes the result
+ *                         without the sign
+ *   WF_AUG_GAMMA_RESTORE  sign ((x - mean_b) / (std_b + 1e-8) * std_a + sign mean_a): stats_a as
+ *                         given to the POW step, stats_b that step's stats_out
+ * fp32 arithmetic on constants rounded from fp64.  stats_out (may be NULL): the statistics of
+ * all N planes after the step, from fp64 partials per workgroup merged in a fixed order;
+ * needs the workspace of wf_augment_pointwise_workspace_bytes(N, S) bytes, 8-byte aligned.
+ * wf_channel_stats is the WF_AUG_NONE form.                                                 */
+enum { WF_AUG_NONE = 0, WF_AUG_SCALE = 1, WF_AUG_CONTRAST = 2, WF_AUG_GAMMA_POW = 3,
+       WF_AUG_GAMMA_RESTORE = 4 };
+int64_t wf_augment_pointwise_workspace_bytes(int64_t N, int64_t S);
+int wf_augment_pointwise(float* x, int64_t N, int64_t S, int op, const double* params,
+                         const double* stats_a, const double* stats_b, double* stats_out,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+int wf_channel_stats(const float* x, int64_t N, int64_t S, double* stats, void* workspace,
+                     int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -163,9 +163,18 @@ SIGNATURES = {
     "wf_select_workspace_bytes": (_I64, [_I64]),
     "wf_select_scan": (_I, [_P, _I64, _I, _I, _P, _I64, _P, _P]),
     "wf_select_pick": (_I, [_P, _I64, _I64, _I64, _I, _I, _P, _I64, _P, _I64, _P, _P, _P, _P]),
+    # train-time augmentation (spline prefilter, samplers, blur, pointwise steps + statistics)
+    "wf_spline_prefilter_axis": (_I, [_P, _P, _I64, _I64, _I64, _I64, _I, _I, _P]),
+    "wf_gauss_blur_axis": (_I, [_P, _P, _I64, _I64, _I64, _I64, _I, _P, _I, _P]),
+    "wf_affine_sample": (_I, [_P, _P, _P] + [_I64] * 7 + [_P, _P, _P]),
+    "wf_zoom_nearest": (_I, [_P] + [_I64] * 7 + [_P, _P]),
+    "wf_zoom_cubic": (_I, [_P] + [_I64] * 7 + [_P, _P]),
+    "wf_augment_pointwise_workspace_bytes": (_I64, [_I64, _I64]),
+    "wf_augment_pointwise": (_I, [_P, _I64, _I64, _I, _P, _P, _P, _P, _P, _I64, _P]),
+    "wf_channel_stats": (_I, [_P, _I64, _I64, _P, _P, _I64, _P]),
 }
 
-ABI_VERSION = 24
+ABI_VERSION = 25
 _lock = threading.Lock()
 _lib = None
 _err = None

@@ -2094,3 +2094,220 @@ class Selection:
             _lib.call("wf_select_pick", self.labels.data_ptr(), D, H, W, self.mode, self.value,
                       self.ws.data_ptr(), self.nbytes, ranks.data_ptr(), nq, *args, _stream())
         return out
+
+
+# ------------------------------------------------------------------------------------------
+# train-time augmentation: spline prefilter, samplers, blur, pointwise steps + statistics
+# (waveformer_amd.augment)
+# ------------------------------------------------------------------------------------------
+SPLINE_MIRROR, SPLINE_EDGE = 0, 1
+SPLINE_PAD = 12
+AUG_NONE, AUG_SCALE, AUG_CONTRAST, AUG_GAMMA_POW, AUG_GAMMA_RESTORE = range(5)
+GAUSS_MAX_RADIUS = 20
+
+
+def _planes4(x: torch.Tensor, who: str, name: str = "x") -> Tuple[int, int, int, int]:
+    _check(x, name)
+    if x.dim() != 4:
+        raise ValueError(f"{who}: expected {name} (N, D, H, W), got {tuple(x.shape)}")
+    return tuple(int(v) for v in x.shape)
+
+
+def _size3(size: Sequence[int], who: str) -> Tuple[int, int, int]:
+    size = tuple(int(v) for v in size)
+    if len(size) != 3 or min(size) < 1:
+        raise ValueError(f"{who}: expected three positive sizes, got {size!r}")
+    return size
+
+
+def spline_prefilter_axis(x: torch.Tensor, axis: int, mode: int = SPLINE_MIRROR) -> torch.Tensor:
+    """scipy's cubic B-spline prefilter along one axis (0 = D, 1 = H, 2 = W) of x (N, D, H, W)
+    (wf_spline_prefilter_axis).  SPLINE_MIRROR keeps the shape; SPLINE_EDGE returns the axis
+    2 * SPLINE_PAD longer (the edge padding of zoom(mode='nearest') stays in the result)."""
+    shape = list(_planes4(x, "spline_prefilter_axis"))
+    if axis not in (0, 1, 2) or mode not in (SPLINE_MIRROR, SPLINE_EDGE):
+        raise ValueError(f"spline_prefilter_axis: bad axis {axis!r} or mode {mode!r}")
+    oshape = list(shape)
+    if mode == SPLINE_EDGE:
+        oshape[1 + axis] += 2 * SPLINE_PAD
+    out = torch.empty(oshape, dtype=torch.float32, device=x.device)
+    _lib.call("wf_spline_prefilter_axis", x.data_ptr(), out.data_ptr(), *shape, int(axis),
+              int(mode), _stream())
+    return out
+
+
+def spline_prefilter(x: torch.Tensor, mode: int = SPLINE_MIRROR) -> torch.Tensor:
+    """The prefilter along D, H and W of x (N, D, H, W): the coefficients affine_sample
+    (SPLINE_MIRROR) or zoom_cubic (SPLINE_EDGE, padded on every axis) evaluate.  In mirror mode
+    an axis of length 1 is skipped, as scipy skips it."""
+    shape = _planes4(x, "spline_prefilter")
+    for axis in range(3):
+        if mode == SPLINE_MIRROR and shape[1 + axis] == 1:
+            continue
+        x = spline_prefilter_axis(x, axis, mode)
+    return x
+
+
+def gaussian_weights(sigma: float, truncate: float = 4.0) -> list:
+    """The centre and one side of scipy.ndimage's normalised Gaussian kernel, in float64."""
+    sigma = float(sigma)
+    if not sigma > 0.0:
+        raise ValueError(f"gaussian_weights: sigma must be positive, got {sigma}")
+    radius = int(truncate * sigma + 0.5)
+    if radius > GAUSS_MAX_RADIUS:
+        raise ValueError(f"gaussian_weights: radius {radius} > {GAUSS_MAX_RADIUS}")
+    phi = [math.exp(-0.5 / (sigma * sigma) * k * k) for k in range(-radius, radius + 1)]
+    total = math.fsum(phi)
+    return [v / total for v in phi[radius:]]
+
+
+def gauss_blur_axis(x: torch.Tensor, axis: int, weights: Sequence[float],
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """scipy.ndimage.gaussian_filter1d (mode 'reflect') along one axis of x (N, D, H, W) with the
+    symmetric kernel weights = [centre, w1, ..., w_radius] (wf_gauss_blur_axis)."""
+    shape = _planes4(x, "gauss_blur_axis")
+    radius = len(weights) - 1
+    if axis not in (0, 1, 2) or not 0 <= radius <= GAUSS_MAX_RADIUS:
+        raise ValueError(f"gauss_blur_axis: bad axis {axis!r} or radius {radius}")
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _check(out, "out")
+        if out.shape != x.shape:
+            raise ValueError(f"gauss_blur_axis: out {tuple(out.shape)} != {tuple(x.shape)}")
+    w = (ctypes.c_float * (radius + 1))(*[float(v) for v in weights])
+    _lib.call("wf_gauss_blur_axis", x.data_ptr(), out.data_ptr(), *shape, int(axis), w, radius,
+              _stream())
+    return out
+
+
+def gauss_blur(x: torch.Tensor, sigma: float) -> torch.Tensor:
+    """scipy.ndimage.gaussian_filter(sigma, order=0) of every plane of x (N, D, H, W): axes D, H,
+    W in turn, mode 'reflect', truncate 4."""
+    w = gaussian_weights(sigma)
+    a = gauss_blur_axis(x, 0, w)
+    b = gauss_blur_axis(a, 1, w)
+    return gauss_blur_axis(b, 2, w, out=a)
+
+
+def affine_sample(coef: Optional[torch.Tensor], seg: Optional[torch.Tensor], matrix,
+                  size: Sequence[int], out: Optional[torch.Tensor] = None,
+                  out_seg: Optional[torch.Tensor] = None
+                  ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """One sample of augment_spatial (wf_affine_sample): coef (C, D, H, W) the mirror-prefiltered
+    channels -> (C, *size) by cubic interpolation with cval 0; seg (D, H, W) fp32 labels ->
+    (*size) by per-label trilinear interpolation (>= 0.5, the largest label wins, else 0).
+    matrix: 3 x 4 float64, input coordinate = matrix[:, :3] @ (o - (size - 1) / 2) + matrix[:, 3]."""
+    size = _size3(size, "affine_sample")
+    flat = [float(v) for row in matrix for v in row]
+    if len(flat) != 12:
+        raise ValueError("affine_sample: matrix must be 3 x 4")
+    if coef is None and seg is None:
+        raise ValueError("affine_sample: coef and seg are both None")
+    C = 1
+    if coef is not None:
+        C, D, H, W = _planes4(coef, "affine_sample", "coef")
+        if out is None:
+            out = torch.empty((C,) + size, dtype=torch.float32, device=coef.device)
+        _check(out, "out")
+        if tuple(out.shape) != (C,) + size:
+            raise ValueError(f"affine_sample: out {tuple(out.shape)} != {(C,) + size}")
+    if seg is not None:
+        _check(seg, "seg")
+        if seg.dim() != 3 or (coef is not None and tuple(seg.shape) != (D, H, W)):
+            raise ValueError(f"affine_sample: seg {tuple(seg.shape)} does not match the data")
+        D, H, W = (int(v) for v in seg.shape)
+        if out_seg is None:
+            out_seg = torch.empty(size, dtype=torch.float32, device=seg.device)
+        _check(out_seg, "out_seg")
+        if tuple(out_seg.shape) != size:
+            raise ValueError(f"affine_sample: out_seg {tuple(out_seg.shape)} != {size}")
+    m = (ctypes.c_double * 12)(*flat)
+    _lib.call("wf_affine_sample", _ptr(coef), _ptr(seg), m, C, D, H, W, *size,
+              _ptr(out) if coef is not None else None, _ptr(out_seg) if seg is not None else None,
+              _stream())
+    return (out if coef is not None else None), (out_seg if seg is not None else None)
+
+
+def zoom_nearest(x: torch.Tensor, size: Sequence[int]) -> torch.Tensor:
+    """scipy.ndimage.zoom(order=0, mode='nearest', grid_mode=True) of x (N, D, H, W) to
+    (N, *size) (wf_zoom_nearest): exact."""
+    N, D, H, W = _planes4(x, "zoom_nearest")
+    size = _size3(size, "zoom_nearest")
+    out = torch.empty((N,) + size, dtype=torch.float32, device=x.device)
+    _lib.call("wf_zoom_nearest", x.data_ptr(), N, D, H, W, *size, out.data_ptr(), _stream())
+    return out
+
+
+def zoom_cubic(coef: torch.Tensor, size: Sequence[int], out: Optional[torch.Tensor] = None
+               ) -> torch.Tensor:
+    """zoom(order=3, mode='nearest', grid_mode=True) to (N, *size) from coef, the padded
+    (N, D + 24, H + 24, W + 24) result of spline_prefilter(x, SPLINE_EDGE) (wf_zoom_cubic)."""
+    N, pD, pH, pW = _planes4(coef, "zoom_cubic", "coef")
+    size = _size3(size, "zoom_cubic")
+    D, H, W = pD - 2 * SPLINE_PAD, pH - 2 * SPLINE_PAD, pW - 2 * SPLINE_PAD
+    if min(D, H, W) < 1:
+        raise ValueError(f"zoom_cubic: coef {tuple(coef.shape)} is not a padded volume")
+    if out is None:
+        out = torch.empty((N,) + size, dtype=torch.float32, device=coef.device)
+    else:
+        _check(out, "out")
+        if tuple(out.shape) != (N,) + size:
+            raise ValueError(f"zoom_cubic: out {tuple(out.shape)} != {(N,) + size}")
+    _lib.call("wf_zoom_cubic", coef.data_ptr(), N, D, H, W, *size, out.data_ptr(), _stream())
+    return out
+
+
+def augment_pointwise(x: torch.Tensor, op: int, params: Optional[torch.Tensor] = None,
+                      stats_a: Optional[torch.Tensor] = None,
+                      stats_b: Optional[torch.Tensor] = None, want_stats: bool = False,
+                      guard: bool = False) -> Optional[torch.Tensor]:
+    """One intensity step in place on x (N, S) fp32 (wf_augment_pointwise): params (N, 4) fp64
+    {drawn, value, sign, 0}, stats_* (N, 4) fp64 {mean, population std, min, max}.  With
+    want_stats returns the statistics of all planes after the step, bitwise repeatable."""
+    _check(x, "x")
+    if x.dim() != 2:
+        raise ValueError(f"augment_pointwise: expected x (N, S), got {tuple(x.shape)}")
+    N, S = (int(v) for v in x.shape)
+    if op not in (AUG_NONE, AUG_SCALE, AUG_CONTRAST, AUG_GAMMA_POW, AUG_GAMMA_RESTORE):
+        raise ValueError(f"augment_pointwise: unknown op {op!r}")
+    need = {"params": op != AUG_NONE, "stats_a": op >= AUG_CONTRAST,
+            "stats_b": op == AUG_GAMMA_RESTORE}
+    for name, t in (("params", params), ("stats_a", stats_a), ("stats_b", stats_b)):
+        if t is None:
+            if need[name]:
+                raise ValueError(f"augment_pointwise: op {op} needs {name}")
+            continue
+        _check(t, name, dtype=torch.float64)
+        if tuple(t.shape) != (N, 4):
+            raise ValueError(f"augment_pointwise: {name} {tuple(t.shape)} != {(N, 4)}")
+    if op == AUG_NONE and not want_stats:
+        raise ValueError("augment_pointwise: nothing to do")
+    stats = ws = None
+    nbytes = 0
+    if want_stats:
+        nbytes = _lib.query("wf_augment_pointwise_workspace_bytes", N, S)
+        ws = _workspace(nbytes, x.device, "wf_augment_pointwise_workspace_bytes", guard)
+        stats = torch.empty((N, 4), dtype=torch.float64, device=x.device)
+    _lib.call("wf_augment_pointwise", x.data_ptr(), N, S, int(op), _ptr(params), _ptr(stats_a),
+              _ptr(stats_b), _ptr(stats), _ptr(ws), nbytes, _stream())
+    if want_stats and guard and not check_guard(ws, nbytes):
+        raise RuntimeError("wf_augment_pointwise wrote past its workspace")
+    return stats
+
+
+def channel_stats(x: torch.Tensor, guard: bool = False) -> torch.Tensor:
+    """(N, 4) fp64 {mean, population std, min, max} of every row of x (N, S) fp32
+    (wf_channel_stats): fp64 partials merged in a fixed order, bitwise repeatable."""
+    _check(x, "x")
+    if x.dim() != 2:
+        raise ValueError(f"channel_stats: expected x (N, S), got {tuple(x.shape)}")
+    N, S = (int(v) for v in x.shape)
+    nbytes = _lib.query("wf_augment_pointwise_workspace_bytes", N, S)
+    ws = _workspace(nbytes, x.device, "wf_augment_pointwise_workspace_bytes", guard)
+    stats = torch.empty((N, 4), dtype=torch.float64, device=x.device)
+    _lib.call("wf_channel_stats", x.data_ptr(), N, S, stats.data_ptr(), ws.data_ptr(), nbytes,
+              _stream())
+    if guard and not check_guard(ws, nbytes):
+        raise RuntimeError("wf_channel_stats wrote past its workspace")
+    return stats
