@@ -567,7 +567,6 @@ using namespace wf;
 
 extern "C" int64_t wf_ccf_ffn_workspace_bytes(int64_t B, int64_t C, int64_t hidden, int64_t D,
                                               int64_t H, int64_t W, int precision) {
-  (void)C;
   const int64_t e = store32(precision) ? 4 : 2;
   const int64_t one = ((B * D * H * W * hidden * e) + 255) & ~(int64_t)255;
   // + the dwconv's per-32-channel-group {mean, M2} of every position (LN2 in the fc loader)
@@ -575,7 +574,9 @@ extern "C" int64_t wf_ccf_ffn_workspace_bytes(int64_t B, int64_t C, int64_t hidd
   // + the pwconv's per-column-chunk LN1 partials (<= hidden / 32 chunks) and their per-row
   // {mean, rstd} (stages 3 / 4: LN1 + GELU applied in the dwconv staging)
   const int64_t s1 = B * D * H * W * 2 * 4;
-  return 2 * one + 2 * ((st + 255) & ~(int64_t)255) + ((s1 + 255) & ~(int64_t)255);
+  // + the stage-3 fc weight in the order ffn_dwfc3_tb streams it (rewritten by every call)
+  const int64_t fcs = C == 192 && hidden == 768 && store32(precision) ? DWFC3_FCS_BYTES : 0;
+  return 2 * one + 2 * ((st + 255) & ~(int64_t)255) + ((s1 + 255) & ~(int64_t)255) + fcs;
 }
 
 extern "C" int wf_ccf_ffn_stage(int stage, const float* xh, const float* stats,
@@ -712,11 +713,19 @@ extern "C" int wf_ccf_ffn_stage(int stage, const float* xh, const float* stats,
   // row in LDS
   const bool no_dwfc = getenv("WF_FFN_NO_DWFC") != nullptr;  // per call: tests switch it
   const bool dwfc1 = C == 48 && hidden == 192, dwfc2 = C == 96 && hidden == 384;
-  if (!keep && !no_dwfc && (dwfc1 || dwfc2)) {
+  // the stage-3 shape has the one fused kernel: fp32 h1 and tensors within its 32-bit offsets
+  const bool dwfc3 = C == 192 && hidden == 768 && store32(precision) && ffn_dwfc3_tb_fits(B, D, H, W);
+  if (!keep && !no_dwfc && (dwfc1 || dwfc2 || dwfc3)) {
     if (stage == 1 || stage == 3) return rc;  // stage 3 (fc) is part of the fused kernel
-    const DwFcArgs d = dwfc_args(h1, dw_w, dw_b, ln2_w, ln2_b, eps2, fc_bf16x2, fc_b, xh, stats,
-                                 n2_w, n2_b, branch_scale, out, B, D, H, W);
-    return dwfc1 ? launch_ffn_dwfc_s1(d, precision, s) : launch_ffn_dwfc2(d, precision, s);
+    DwFcArgs d = dwfc_args(h1, dw_w, dw_b, ln2_w, ln2_b, eps2, fc_bf16x2, fc_b, xh, stats, n2_w,
+                           n2_b, branch_scale, out, B, D, H, W);
+    if (dwfc3)  // the workspace's tail
+      d.fcs = reinterpret_cast<uint16_t*>(
+          reinterpret_cast<char*>(workspace) +
+          wf_ccf_ffn_workspace_bytes(B, C, hidden, D, H, W, precision) - DWFC3_FCS_BYTES);
+    return dwfc1   ? launch_ffn_dwfc_s1(d, precision, s)
+           : dwfc2 ? launch_ffn_dwfc2(d, precision, s)
+                   : launch_ffn_dwfc3(d, precision, s);
   }
   const bool split_ln = hidden % 32 == 0;
   WF_REQUIRE(!keep || split_ln, "training needs hidden % 32 == 0 (h2 kept pre-LayerNorm)");

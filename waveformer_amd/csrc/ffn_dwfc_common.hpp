@@ -1,5 +1,6 @@
 // ffn_dwfc_common.hpp -- what the CCF_FFN back-half kernels share (ffn_dwfc.hip: ffn_dwfc_sb,
-// ffn_dwfc2; ffn_dwfc_tb.hip: ffn_dwfc_tb4; ffn_dwfc2_tb.hip: ffn_dwfc2_tb; ffn_fused.hip):
+// ffn_dwfc2; ffn_dwfc_tb.hip: ffn_dwfc_tb4; ffn_dwfc2_tb.hip: ffn_dwfc2_tb; ffn_dwfc3_tb.hip:
+// ffn_dwfc3_tb; ffn_fused.hip):
 // the argument block and launchers, the tile decode, the wave roles, the LN2 row, the bf16x3
 // MFMA step, the staging of the small vectors, the epilogue expression and the buffer
 // descriptors.  The helpers are parameterised by geometry only.  Not here, on purpose: the
@@ -11,8 +12,8 @@
 namespace wf {
 
 // ---- CCF_FFN back half fused: dwconv + bias + LN2 + GELU + fc + bias + the Block's Q4
-// residual, for C = 48, hidden = 192 and C = 96, hidden = 384 (h1 fp32 for PREC_SPLIT /
-// PREC_FP16, bf16 for PREC_BF16)
+// residual, for C = 48, hidden = 192, C = 96, hidden = 384 and C = 192, hidden = 768 (h1 fp32
+// for PREC_SPLIT / PREC_FP16, bf16 for PREC_BF16)
 struct DwFcArgs {
   const void* h1;        // (B, D, H, W, HID) fp32 (SPLIT) or bf16
   const float* dw_w;     // (HID, 27)
@@ -36,7 +37,12 @@ struct DwFcArgs {
   const float* ln1_b;
   float eps1;
   int dbg;               // timing experiments only (builds with WF_FFN_DBG=1): phases skipped
+  // ffn_dwfc3_tb only: DWFC3_FCS_BYTES of workspace for the fc weight in stream order
+  uint16_t* fcs;
 };
+// the stage-3 fc weight (192 x 768 bf16 hi + lo) rewritten per call as the 1-KB fragments the E
+// waves of ffn_dwfc3_tb stream: the tail of wf_ccf_ffn_workspace_bytes at that shape
+constexpr int64_t DWFC3_FCS_BYTES = 2 * 192 * 768 * 2;
 #ifndef WF_FFN_DBG  // 1: timing-experiment build (DwFcArgs::dbg phase skips; never the shipped library)
 #define WF_FFN_DBG 0
 #endif
@@ -57,6 +63,10 @@ int launch_ffn_dwfc_tb4(const DwFcArgs& a, int prec, hipStream_t s);
 int launch_ffn_dwfc2(const DwFcArgs& a, int prec, hipStream_t s);
 // three depthwise waves + one fc wave per SIMD (ffn_dwfc2_tb.hip); ZS set by the caller
 int launch_ffn_dwfc2_tb(const DwFcArgs& a, int prec, hipStream_t s);
+// the stage-3 shape, C = 192, hidden = 768, fp32 h1 (ffn_dwfc3_tb.hip): 4 x 4 tiles, direct
+// depthwise loads, three h2 tiles in LDS, the fc weight streamed from L2 into registers; sets
+// ZS.  Only where ffn_dwfc3_tb_fits: the caller keeps the staged path for the rest
+int launch_ffn_dwfc3(const DwFcArgs& a, int prec, hipStream_t s);
 // ---- the whole CCF_FFN + norm2 + Q4 residual in one kernel for C = 48, hidden = 192: the
 // haloed h1 plane is computed in LDS from the x rows (pw MFMA + LN1 + GELU), never stored
 int launch_ffn_fused(const DwFcArgs& a, int prec, hipStream_t s);
@@ -73,6 +83,9 @@ inline bool ffn_dwfc_tb4_fits(const DwFcArgs& a) {
 inline bool ffn_dwfc2_tb_fits(const DwFcArgs& a) {
   return (int64_t)a.B * a.D * a.H * a.W * 96 * 4 < ((int64_t)1 << 31) &&
          ((int64_t)a.H * a.W + 8) * 384 * 4 < ((int64_t)1 << 31);
+}
+inline bool ffn_dwfc3_tb_fits(int64_t B, int64_t D, int64_t H, int64_t W) {
+  return B * D * H * W * 192 * 4 < ((int64_t)1 << 31) && (H * W + 8) * 768 * 4 < ((int64_t)1 << 31);
 }
 
 // h1 plane staging: fp32 (SPLIT / FP16 workspaces) or bf16 (BF16) rows widened to fp32
