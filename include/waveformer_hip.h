@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define WF_ABI_VERSION 25
+#define WF_ABI_VERSION 26
 
 enum { WF_PREC_BF16 = 0, WF_PREC_BF16X3 = 1, WF_PREC_FP16 = 2 };
 
@@ -532,6 +532,23 @@ int wf_ccf_ffn_stage(int stage, const float* xh, const float* stats, const float
                      const uint16_t* fc_bf16x2, const float* fc_b, const float* branch_scale,
                      float* out, void* workspace, int64_t B, int64_t C, int64_t hidden,
                      int64_t D, int64_t H, int64_t W, int precision, void* stream);
+/* Host only (no launch): what wf_ccf_ffn_stage does for this shape, computed by the functions it
+ * uses, with the environment switches (WF_FFN_FUSED, WF_FFN_NO_DWFC, WF_FFN_LN1_FUSE) as a call
+ * in this process would see them.  train: the stage | 16 flag.  Returns front | back << 8, or a
+ * negative WF_E_* with wf_last_error set (a bad shape or precision; train with hidden % 32 != 0).
+ *   front, how h1 = GELU(LN1(pwconv)) is formed: 0 LN1 + GELU in the pwconv GEMM's epilogue;
+ *     1 plain store, then wf_ln_act_fwd in place; 2 LN1 partials + finalize, applied in the
+ *     depthwise conv's staging; 3 nothing launched (the whole-FFN kernel).
+ *   back, what runs dwconv + LN2 + GELU + fc + residual: 0 ffn_fused (the whole FFN);
+ *     1 ffn_dwfc_tb4; 2 ffn_dwfc_sb; 3 ffn_dwfc2_tb; 4 ffn_dwfc2_kernel; 5 ffn_dwfc3_tb;
+ *     6 staged, dwconv3d then the fc GEMM with LN2 + GELU in its loader; 7 staged,
+ *     dwconv_ln_gelu then the plain fc GEMM.  Backs 0-5 are one kernel: it is stage 2, and
+ *     stage 3 (for back 0 also stage 1) is a no-op.
+ * offsets: NULL, or 7 values: the byte offsets in the workspace of h1, h2, the depthwise conv's
+ * LN2 partials, the pwconv's LN1 partials, the per-row LN1 {mean, rstd} and the stage-3 fc
+ * stream area (-1 where the shape has none), then the total (== wf_ccf_ffn_workspace_bytes).  */
+int wf_ccf_ffn_plan(int64_t B, int64_t C, int64_t hidden, int64_t D, int64_t H, int64_t W,
+                    int precision, int train, int64_t* offsets);
 
 /* ---- a9: PatchMerging (quirk Q3) ------------------------------------------------------ */
 /* Replaces PatchMerging.forward (wave_helper.py:173-194): the 8-way strided gather with its

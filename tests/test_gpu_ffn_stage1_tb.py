@@ -10,65 +10,21 @@ import functools
 
 import pytest
 import torch
-import torch.nn.functional as F
 
-from oracle import ref_waveformer as R
-from oracle.weight_rule import rule_state_dict, seeded_randn
 from tests import cases as C
+from tests import ffn_cases
+from tests.ffn_cases import _gpu  # noqa: F401  (autouse)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-CH = 48
+CH, SEEDS = 48, (34, 35, 36)
 BARS = {"bf16x3": 5e-5, "fp16": 2e-3}
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from waveformer_amd import _lib
-    _lib.load()  # fail loudly if the HIP library is missing
-    yield
-
-
-@functools.lru_cache(maxsize=None)
-def _setup(shape):
-    """Module, norm2, input, per-sample factors and the oracle's outputs (Block and bare form)
-    of one shape: computed once, shared by every test of that shape, never modified."""
-    import waveformer_amd.network_models as NM
-    B = shape[0]
-    mlp = NM.CCF_FFN(CH, 4 * CH, img_size=shape[1:])
-    sd = rule_state_dict(mlp.state_dict())
-    mlp.load_state_dict(sd)
-    mlp = mlp.eval().to(DEV)
-    norm2 = torch.nn.LayerNorm(CH, eps=1e-6)
-    with torch.no_grad():
-        norm2.weight.copy_(seeded_randn((CH,), 34) * 0.2 + 1)
-        norm2.bias.copy_(seeded_randn((CH,), 35) * 0.1)
-    x = seeded_randn(shape + (CH,), 36)
-    bs = torch.tensor([0.5, 2.0, 1.0][:B])
-    with torch.no_grad():
-        n2 = F.layer_norm(x, [CH], norm2.weight, norm2.bias, 1e-6)
-        ref_block = x + R.ccf_ffn(sd, "", n2) * bs.view(-1, 1, 1, 1, 1)
-        ref_bare = x + (R.ccf_ffn(sd, "", x) - x) * bs.view(-1, 1, 1, 1, 1)
-    return mlp, norm2.to(DEV), x, bs, {True: ref_block, False: ref_bare}
-
-
-def _run(shape, block, prec, sel=None):
-    """ops.ccf_ffn on the whole batch of `shape`, or on its sample `sel` alone (B = 1)."""
-    from waveformer_amd import ops
-    mlp, norm2, x, bs, _ = _setup(shape)
-    if sel is not None:
-        x, bs = x[sel:sel + 1], bs[sel:sel + 1]
-    with torch.no_grad(), ops.precision(prec):
-        xc = x.to(DEV)
-        stats = ops.msfuse([], xc, 1e-6)[1] if block else None
-        return ops.ccf_ffn(xc, stats, norm2 if block else None, mlp, bs.to(DEV))
+_run = functools.partial(ffn_cases.run, CH, SEEDS)  # (shape, block, prec, sel=None)
+_ref = functools.partial(ffn_cases.ref, CH, SEEDS)  # (shape, block)
 
 
 def _check(shape, block, prec):
-    ref = _setup(shape)[4][block]
+    ref = _ref(shape, block)
     err = C.rel_l2(_run(shape, block, prec), ref)
     print(f"rel-L2 {err:.3e}")
     assert err <= BARS[prec]

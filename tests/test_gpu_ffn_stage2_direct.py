@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from tests import cases as C
-from tests.test_gpu_ffn_stage2_tb import BARS, _gpu, _run, _setup  # noqa: F401  (_gpu: autouse)
+from tests.test_gpu_ffn_stage2_tb import BARS, _gpu, _ref, _run  # noqa: F401  (_gpu: autouse)
 
 pytestmark = pytest.mark.gpu
 
@@ -30,8 +30,7 @@ HALO = [(1, 3, 1, 1), (1, 3, 2, 3), (1, 3, 5, 7), (1, 3, 8, 8), (2, 3, 4, 4)]
 @pytest.mark.parametrize("block", [False, True])
 @pytest.mark.parametrize("prec", ["bf16x3", "fp16"])
 def test_stage2_direct_vs_oracle(shape, block, prec):
-    ref = _setup(shape)[4][block]
-    err = C.rel_l2(_run(shape, block, prec), ref)
+    err = C.rel_l2(_run(shape, block, prec), _ref(shape, block))
     print(f"rel-L2 {err:.3e}")
     assert err <= BARS[prec]
 

@@ -8,72 +8,17 @@ import functools
 
 import pytest
 import torch
-import torch.nn.functional as F
 
-from oracle import ref_waveformer as R
-from oracle.weight_rule import rule_state_dict, seeded_randn
 from tests import cases as C
+from tests import ffn_cases
+from tests.ffn_cases import _gpu  # noqa: F401  (autouse)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-CH = 192
+CH, SEEDS = 192, (37, 38, 39)
 BARS = {"bf16x3": 5e-5, "fp16": 2e-3}
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from waveformer_amd import _lib
-    _lib.load()  # fail loudly if the HIP library is missing
-    yield
-
-
-@functools.lru_cache(maxsize=None)
-def _model(shape):
-    """Module, norm2, input, per-sample factors and the state dict of one shape: made once,
-    shared by every test of that shape, never modified."""
-    import waveformer_amd.network_models as NM
-    mlp = NM.CCF_FFN(CH, 4 * CH, img_size=shape[1:])
-    sd = rule_state_dict(mlp.state_dict())
-    mlp.load_state_dict(sd)
-    mlp = mlp.eval().to(DEV)
-    norm2 = torch.nn.LayerNorm(CH, eps=1e-6)
-    with torch.no_grad():
-        norm2.weight.copy_(seeded_randn((CH,), 37) * 0.2 + 1)
-        norm2.bias.copy_(seeded_randn((CH,), 38) * 0.1)
-    x = seeded_randn(shape + (CH,), 39)
-    bs = torch.tensor([0.5, 2.0, 1.0][:shape[0]])
-    return mlp, norm2, x, bs, sd
-
-
-@functools.lru_cache(maxsize=None)
-def _ref(shape, block):
-    """The oracle's output of one shape and form (CPU, fp32): computed once."""
-    _, norm2, x, bs, sd = _model(shape)
-    with torch.no_grad():
-        if block:
-            n2 = F.layer_norm(x, [CH], norm2.weight, norm2.bias, 1e-6)
-            return x + R.ccf_ffn(sd, "", n2) * bs.view(-1, 1, 1, 1, 1)
-        return x + (R.ccf_ffn(sd, "", x) - x) * bs.view(-1, 1, 1, 1, 1)
-
-
-@functools.lru_cache(maxsize=None)
-def _norm2_dev():
-    return _model((1, 1, 1, 1))[1].to(DEV)
-
-
-def _run(shape, block, prec, sel=None):
-    """ops.ccf_ffn on the whole batch of `shape`, or on its sample `sel` alone (B = 1)."""
-    from waveformer_amd import ops
-    mlp, _, x, bs, _ = _model(shape)
-    if sel is not None:
-        x, bs = x[sel:sel + 1], bs[sel:sel + 1]
-    with torch.no_grad(), ops.precision(prec):
-        xc = x.to(DEV)
-        stats = ops.msfuse([], xc, 1e-6)[1] if block else None
-        return ops.ccf_ffn(xc, stats, _norm2_dev() if block else None, mlp, bs.to(DEV))
+_run = functools.partial(ffn_cases.run, CH, SEEDS)  # (shape, block, prec, sel=None)
+_ref = functools.partial(ffn_cases.ref, CH, SEEDS)  # (shape, block)
 
 
 # The segment rule (launch_ffn_dwfc3): ZS = D, halved (rounding up) while ZS > 8 and B x tiles x

@@ -105,6 +105,7 @@ SIGNATURES = {
                             _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _P]),
     "wf_ccf_ffn_stage": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _F, _P,
                               _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _P]),
+    "wf_ccf_ffn_plan": (_I, [_I64, _I64, _I64, _I64, _I64, _I64, _I, _I, _P]),
     "wf_patch_merging_fwd": (_I, [_P, _P, _P, _F, _P, _I, _P, _I64, _I64, _I64, _I64, _I64,
                                   _I, _P]),
     "wf_proj_out_fwd": (_I, [_P, _P, _I, _F, _I64, _I64, _I64, _P]),
@@ -174,7 +175,7 @@ SIGNATURES = {
     "wf_channel_stats": (_I, [_P, _I64, _I64, _P, _P, _I64, _P]),
 }
 
-ABI_VERSION = 25
+ABI_VERSION = 26
 _lock = threading.Lock()
 _lib = None
 _err = None

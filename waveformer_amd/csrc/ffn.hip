@@ -8,7 +8,8 @@
 // and the Block adds it to attn_fused again: out = x + (n + fc(h2)), n = norm2(x)   :509
 // Launches: gemm(pw, LN2 of x in the loader, LN+GELU epilogue) -> dwconv_ln_gelu ->
 //           gemm(fc, residual epilogue).  h1/h2 live in the caller's workspace (bf16 for
-//           PREC_BF16, fp32 for PREC_SPLIT).
+//           PREC_BF16, fp32 for PREC_SPLIT).  That is the general form; which kernels a
+//           call takes and where its workspace areas lie is ffn_plan.hpp's decision.
 #include "kernels.hpp"
 
 namespace wf {
@@ -561,22 +562,124 @@ static DwFcArgs dwfc_args(const void* h1, const float* dw_w, const float* dw_b, 
   return d;
 }
 
+static_assert(kFfnPrecBf16 == PREC_BF16, "ffn_plan.hpp's storage rule is store32");
+
+// h1 = GELU(LN1(pwconv(norm2?(x)) + bias)) into (M, hidden): the LN1 + GELU epilogue form (the
+// other front forms store plainly, EPI_STORE)
+static GemmArgs pwconv_gemm_args(const float* xh, const float* stats, const float* n2_w,
+                                 const float* n2_b, const uint16_t* pw, const float* pw_b,
+                                 const float* ln1_w, const float* ln1_b, float eps1, void* h1,
+                                 int64_t M, int64_t C, int64_t hidden, int prec) {
+  GemmArgs g{};
+  g.prec = prec;
+  g.a_src = xh;
+  g.a_bf16 = 0;
+  g.a_C = (int)C;
+  g.a_nseg = 1;
+  g.a_map = MAP_IDENTITY;
+  g.a_ln = stats ? LN_GIVEN : LN_NONE;
+  g.a_stats = stats;
+  g.a_ln_w = n2_w;
+  g.a_ln_b = n2_b;
+  g.w = pw;
+  g.M = M;
+  g.N = (int)hidden;
+  g.K = (int)C;
+  g.epi = EPI_LN_GELU;
+  g.bias = pw_b;
+  g.e_ln_w = ln1_w;
+  g.e_ln_b = ln1_b;
+  g.e_eps = eps1;
+  g.out = h1;
+  g.out_bf16 = !store32(prec);
+  g.ldo = hidden;
+  return g;
+}
+
+// out = x + (norm2?(x) + fc(.) + bias) * branch_scale over the rows of h2: GELU(LN2(h2)) formed
+// in the loader from the dwconv's partials ln2_pst, or (ln2_pst NULL) h2 taken as it is
+static GemmArgs fc_gemm_args(const void* h2, const float* ln2_pst, const float* ln2_w,
+                             const float* ln2_b, float eps2, const uint16_t* fc,
+                             const float* fc_b, const float* xh, const float* stats,
+                             const float* n2_w, const float* n2_b, const float* branch_scale,
+                             float* out, int64_t M, int64_t C, int64_t hidden,
+                             int64_t rows_per_sample, int prec) {
+  GemmArgs f{};
+  f.prec = prec;
+  f.a_src = h2;
+  f.a_bf16 = !store32(prec);
+  f.a_C = (int)hidden;
+  f.a_nseg = 1;
+  f.a_map = MAP_IDENTITY;
+  f.a_ln = ln2_pst ? LN_PARTIAL : LN_NONE;
+  if (ln2_pst) {
+    f.a_stats = ln2_pst;
+    f.a_np = (int)(hidden / DW_STAT_GROUP);
+    f.a_ln_w = ln2_w;
+    f.a_ln_b = ln2_b;
+    f.a_eps = eps2;
+    f.a_gelu = 1;
+  }
+  f.w = fc;
+  f.M = M;
+  f.N = (int)C;
+  f.K = (int)hidden;
+  f.epi = EPI_RESID;
+  f.bias = fc_b;
+  f.r_x = xh;
+  f.r_stats = stats;
+  f.r_ln_w = n2_w;
+  f.r_ln_b = n2_b;
+  f.r_scale = branch_scale;
+  f.rows_per_sample = rows_per_sample;
+  f.out = out;
+  f.ldo = C;
+  return f;
+}
+
+// The plan of a call, or what is wrong with it: the shape, then ffn_plan under the environment
+// switches as a call in this process sees them, then the one input the plain
+// header cannot compute -- gemm_kc's column chunk for the plain-store pwconv of the partials form
+static const char* ffn_plan_call(int64_t B, int64_t C, int64_t hidden, int64_t D, int64_t H,
+                                 int64_t W, int prec, bool train, FfnPlan& p) {
+  if (!(B >= 1 && D >= 1 && H >= 1 && W >= 1)) return "empty volume";
+  if (!(C % 8 == 0 && hidden % 8 == 0)) return "C and hidden must be multiples of 8";
+  if (!valid_prec(prec)) return "unknown precision";
+  static const bool ln1_fuse = getenv("WF_FFN_LN1_FUSE") != nullptr;  // latched
+  FfnSwitches sw;
+  sw.whole = getenv("WF_FFN_FUSED") != nullptr;      // per call: tests switch it
+  sw.no_dwfc = getenv("WF_FFN_NO_DWFC") != nullptr;  // per call: tests switch it
+  sw.ln1_fuse = ln1_fuse;
+  const char* why = ffn_plan(B, C, hidden, D, H, W, prec, train, sw, p);
+  if (!why && p.front == FFN_FRONT_PARTIALS) {  // only the GEMM's shape is read
+    GemmArgs pw = pwconv_gemm_args(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                   nullptr, 0.f, nullptr, B * D * H * W, C, hidden, prec);
+    pw.epi = EPI_STORE;
+    ffn_plan_set_kc_chunk(p, hidden, gemm_kc_pick_nt(pw));
+  }
+  return why;
+}
+
 }  // namespace wf
 
 using namespace wf;
 
 extern "C" int64_t wf_ccf_ffn_workspace_bytes(int64_t B, int64_t C, int64_t hidden, int64_t D,
                                               int64_t H, int64_t W, int precision) {
-  const int64_t e = store32(precision) ? 4 : 2;
-  const int64_t one = ((B * D * H * W * hidden * e) + 255) & ~(int64_t)255;
-  // + the dwconv's per-32-channel-group {mean, M2} of every position (LN2 in the fc loader)
-  const int64_t st = B * D * H * W * (hidden / DW_STAT_GROUP) * 2 * 4;
-  // + the pwconv's per-column-chunk LN1 partials (<= hidden / 32 chunks) and their per-row
-  // {mean, rstd} (stages 3 / 4: LN1 + GELU applied in the dwconv staging)
-  const int64_t s1 = B * D * H * W * 2 * 4;
-  // + the stage-3 fc weight in the order ffn_dwfc3_tb streams it (rewritten by every call)
-  const int64_t fcs = C == 192 && hidden == 768 && store32(precision) ? DWFC3_FCS_BYTES : 0;
-  return 2 * one + 2 * ((st + 255) & ~(int64_t)255) + ((s1 + 255) & ~(int64_t)255) + fcs;
+  return ffn_workspace(B * D * H * W, C, hidden, precision).bytes;
+}
+
+extern "C" int wf_ccf_ffn_plan(int64_t B, int64_t C, int64_t hidden, int64_t D, int64_t H,
+                               int64_t W, int precision, int train, int64_t* offsets) {
+  FfnPlan plan;
+  if (const char* why = ffn_plan_call(B, C, hidden, D, H, W, precision, train != 0, plan))
+    return fail(WF_E_SHAPE, std::string(__func__) + ": " + why);
+  if (offsets) {
+    const FfnWorkspace ws = ffn_workspace(B * D * H * W, C, hidden, precision);
+    const int64_t o[7] = {ws.h1, ws.h2, ws.ln2_pst, ws.ln1_pst, ws.ln1_st, ws.fcs, ws.bytes};
+    for (int i = 0; i < 7; ++i) offsets[i] = o[i];
+  }
+  return plan.front | plan.back << 8;
 }
 
 extern "C" int wf_ccf_ffn_stage(int stage, const float* xh, const float* stats,
@@ -588,14 +691,18 @@ extern "C" int wf_ccf_ffn_stage(int stage, const float* xh, const float* stats,
                                 const float* fc_b, const float* branch_scale, float* out,
                                 void* workspace, int64_t B, int64_t C, int64_t hidden,
                                 int64_t D, int64_t H, int64_t W, int precision, void* stream) {
-  // bit 4: training -- take the staged path even where the fused back half exists, so the
-  // workspace keeps h1 = GELU(LN1(pwconv)) and h2 = dwconv (pre-LN2) for the backward
-  const bool keep = (stage & 16) != 0;
-  stage &= ~16;
-  WF_REQUIRE(stage >= 0 && stage <= 3, "stage must be 0 (all), 1 (pwconv), 2 (dwconv) or 3 (fc)");
-  WF_REQUIRE(B >= 1 && D >= 1 && H >= 1 && W >= 1, "empty volume");
-  WF_REQUIRE(C % 8 == 0 && hidden % 8 == 0, "C and hidden must be multiples of 8");
-  WF_REQUIRE(valid_prec(precision), "unknown precision");
+  // ---- the stage: which of the three launches run.  Bit 4: training -- the staged path even
+  // where a fused back half exists, so the workspace keeps h1 = GELU(LN1(pwconv)) and h2 =
+  // dwconv (pre-LN2) for the backward
+  const bool train = (stage & 16) != 0;
+  const int which = stage & ~16;
+  WF_REQUIRE(which >= 0 && which <= 3, "stage must be 0 (all), 1 (pwconv), 2 (dwconv) or 3 (fc)");
+  const bool run_pw = which == 0 || which == 1, run_dw = which == 0 || which == 2,
+             run_fc = which == 0 || which == 3;
+  // ---- validate, and plan
+  FfnPlan plan;
+  if (const char* why = ffn_plan_call(B, C, hidden, D, H, W, precision, train, plan))
+    return fail(WF_E_SHAPE, std::string(__func__) + ": " + why);
   WF_REQUIRE_PTR(xh);
   WF_REQUIRE_PTR(pw_bf16x2);
   WF_REQUIRE_PTR(ln1_w);
@@ -611,173 +718,73 @@ extern "C" int wf_ccf_ffn_stage(int stage, const float* xh, const float* stats,
     WF_REQUIRE_PTR(n2_w);
     WF_REQUIRE_PTR(n2_b);
   }
+  // ---- workspace
   hipStream_t s = (hipStream_t)stream;
   const int64_t M = B * D * H * W;
-  const int64_t e = store32(precision) ? 4 : 2;
-  const int64_t one = ((M * hidden * e) + 255) & ~(int64_t)255;
-  void* h1 = workspace;
-  void* h2 = reinterpret_cast<char*>(workspace) + one;
-  const int hbf = !store32(precision);
-
-  GemmArgs g{};
-  g.prec = precision;
-  g.a_src = xh;
-  g.a_bf16 = 0;
-  g.a_C = (int)C;
-  g.a_nseg = 1;
-  g.a_map = MAP_IDENTITY;
-  g.a_ln = stats ? LN_GIVEN : LN_NONE;
-  g.a_stats = stats;
-  g.a_ln_w = n2_w;
-  g.a_ln_b = n2_b;
-  g.w = pw_bf16x2;
-  g.M = M;
-  g.N = (int)hidden;
-  g.K = (int)C;
-  g.epi = EPI_LN_GELU;
-  g.bias = pw_b;
-  g.e_ln_w = ln1_w;
-  g.e_ln_b = ln1_b;
-  g.e_eps = eps1;
-  g.out = h1;
-  g.out_bf16 = hbf;
-  g.ldo = hidden;
+  const FfnWorkspace ws = ffn_workspace(M, C, hidden, precision);
+  char* base = reinterpret_cast<char*>(workspace);
+  void* h1 = base + ws.h1;
+  void* h2 = base + ws.h2;
+  float* ln2_pst = reinterpret_cast<float*>(base + ws.ln2_pst);
+  float* ln1_pst = reinterpret_cast<float*>(base + ws.ln1_pst);
+  float* ln1_st = reinterpret_cast<float*>(base + ws.ln1_st);
+  GemmArgs pw = pwconv_gemm_args(xh, stats, n2_w, n2_b, pw_bf16x2, pw_b, ln1_w, ln1_b, eps1, h1, M,
+                                 C, hidden, precision);
+  // ---- front: pwconv + LN1 + GELU
   int rc = 0;
-  // wide hidden rows (stages 3 / 4: 4C = 768, 1536): a LayerNorm epilogue needs the whole
-  // row in one workgroup, which only the A-resident gemm_ares can hold -- it then re-streams
-  // the full weight per 16 rows (measured 107 / 145 us per launch at B = 4).  Instead: the
-  // K-chunked GEMM with a plain bias epilogue, then one in-place LayerNorm + GELU row pass.
-  // Round 5: gemm_lnw with 8 / 16-wave workgroups holds the whole 768 / 1536-wide row (the
-  // columns split over the waves), so the LayerNorm + GELU run in its epilogue and the
-  // separate pass is gone for the shapes it takes
-  const bool split_ln1 = store32(precision) && hidden >= 768 && hidden <= 1536 &&
-                         !gemm_lnw_wide_shape(g);
-  // C = 48 / hidden = 192 (stage 1), opt-in (WF_FFN_FUSED=1): the whole FFN in one kernel
-  // (ffn_fused.hip), h1 and h2 stay on chip; stage 2 is that kernel, stages 1 and 3 are part
-  // of it.  Off by default: recomputing the 4 x 8 tile's haloed h1 plane (1.875x the pw GEMM,
-  // LN1 and GELU) costs more VALU time than the h1 round trip through HBM it saves
-  const bool whole = getenv("WF_FFN_FUSED") != nullptr;  // per call: tests switch it
-  if (!keep && whole && C == 48 && hidden == 192) {
-    if (stage == 1 || stage == 3) return 0;
-    DwFcArgs d = dwfc_args(nullptr, dw_w, dw_b, ln2_w, ln2_b, eps2, fc_bf16x2, fc_b, xh, stats, n2_w,
-                           n2_b, branch_scale, out, B, D, H, W);
-    d.pw = pw_bf16x2;
-    d.pw_b = pw_b;
-    d.ln1_w = ln1_w;
-    d.ln1_b = ln1_b;
-    d.eps1 = eps1;
-    return launch_ffn_fused(d, precision, s);
-  }
-  // stages 3 / 4 at inference, WF_FFN_LN1_FUSE=1: the pwconv epilogue writes LN1 partials, a
-  // finalize pass makes the per-row {mean, rstd}, and the dwconv applies LN1 + GELU while
-  // staging its planes (no separate LayerNorm + GELU pass over h1).  Training (keep) stores
-  // h1 = GELU(LN1(.)) for the backward: the pass stays.
-  // opt-in (WF_FFN_LN1_FUSE=1): the LN1 + GELU in the staging measured slower than the
-  // separate pass -- the depthwise conv 64 -> 130 us (stage 3) and 36 -> 82 us (stage 4)
-  // against 44 / 21 us for ln_act_fwd (round 4): the halo-redundant GELU on the staging
-  // lanes costs more than the h1 round trip through HBM at these small shapes
-  static const bool ln1_pass = getenv("WF_FFN_LN1_FUSE") == nullptr;
-  const int64_t stq = ((M * (hidden / DW_STAT_GROUP) * 2 * 4) + 255) & ~(int64_t)255;
-  float* pw_pst = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + 2 * one + stq);
-  float* ln1_st = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + 2 * one + 2 * stq);
-  int pw_np = 0;
-  if (split_ln1 && !keep && !ln1_pass && hidden % DW_STAT_GROUP == 0) {
-    GemmArgs g2 = g;
-    g2.epi = EPI_STORE;
-    const int nt = gemm_kc_pick_nt(g2);
-    if (nt > 0 && hidden % (16 * nt) == 0) pw_np = (int)(hidden / (16 * nt));
-  }
-  if (stage == 0 || stage == 1) {
-    if (split_ln1 && pw_np > 0) {
-      GemmArgs g2 = g;
-      g2.epi = EPI_STORE;
-      g2.o_pstats = pw_pst;
-      rc = launch_gemm(g2, s, "wf_ccf_ffn_fwd(pwconv)");
-      if (!rc)
-        rc = launch_ln_stats_finalize(pw_pst, pw_np, (int)(hidden / pw_np), eps1, ln1_st, M, s);
-    } else if (split_ln1) {
-      GemmArgs g2 = g;
-      g2.epi = EPI_STORE;
-      rc = launch_gemm(g2, s, "wf_ccf_ffn_fwd(pwconv)");
-      if (!rc)
-        rc = wf_ln_act_fwd(reinterpret_cast<const float*>(h1), ln1_w, ln1_b, eps1, 1,
-                           reinterpret_cast<float*>(h1), M, hidden, stream);
-    } else {
-      rc = launch_gemm(g, s, "wf_ccf_ffn_fwd(pwconv)");
-    }
+  if (run_pw && plan.front != FFN_FRONT_NONE) {
+    if (plan.front != FFN_FRONT_EPILOGUE) pw.epi = EPI_STORE;
+    if (plan.front == FFN_FRONT_PARTIALS) pw.o_pstats = ln1_pst;
+    rc = launch_gemm(pw, s, "wf_ccf_ffn_fwd(pwconv)");
+    if (!rc && plan.front == FFN_FRONT_PASS)
+      rc = wf_ln_act_fwd(reinterpret_cast<const float*>(h1), ln1_w, ln1_b, eps1, 1,
+                         reinterpret_cast<float*>(h1), M, hidden, stream);
+    if (!rc && plan.front == FFN_FRONT_PARTIALS)
+      rc = launch_ln_stats_finalize(ln1_pst, plan.ln1_np, (int)(hidden / plan.ln1_np), eps1,
+                                    ln1_st, M, s);
   }
   if (rc) return rc;
-  // dwconv + LN2 + GELU (+ fc + residual): the stage-1 and stage-2 shapes run the fused back
-  // half (ffn_dwfc.hip, h2 stays on chip); other shapes run the z-marching depthwise conv with
-  // LN2 + GELU moved into the fc loader, or (hidden % 32 != 0) fuse dwconv + LN over the full 4C
-  // row in LDS
-  const bool no_dwfc = getenv("WF_FFN_NO_DWFC") != nullptr;  // per call: tests switch it
-  const bool dwfc1 = C == 48 && hidden == 192, dwfc2 = C == 96 && hidden == 384;
-  // the stage-3 shape has the one fused kernel: fp32 h1 and tensors within its 32-bit offsets
-  const bool dwfc3 = C == 192 && hidden == 768 && store32(precision) && ffn_dwfc3_tb_fits(B, D, H, W);
-  if (!keep && !no_dwfc && (dwfc1 || dwfc2 || dwfc3)) {
-    if (stage == 1 || stage == 3) return rc;  // stage 3 (fc) is part of the fused kernel
-    DwFcArgs d = dwfc_args(h1, dw_w, dw_b, ln2_w, ln2_b, eps2, fc_bf16x2, fc_b, xh, stats, n2_w,
-                           n2_b, branch_scale, out, B, D, H, W);
-    if (dwfc3)  // the workspace's tail
-      d.fcs = reinterpret_cast<uint16_t*>(
-          reinterpret_cast<char*>(workspace) +
-          wf_ccf_ffn_workspace_bytes(B, C, hidden, D, H, W, precision) - DWFC3_FCS_BYTES);
-    return dwfc1   ? launch_ffn_dwfc_s1(d, precision, s)
-           : dwfc2 ? launch_ffn_dwfc2(d, precision, s)
-                   : launch_ffn_dwfc3(d, precision, s);
+  // ---- back, one kernel: dwconv + LN2 + GELU + fc + residual is the dwconv stage, the fc stage
+  // is part of it (and so is the pwconv stage of the whole-FFN kernel)
+  if (ffn_back_fused(plan.back)) {
+    if (!run_dw) return 0;
+    DwFcArgs d = dwfc_args(plan.back == FFN_BACK_FUSED ? nullptr : h1, dw_w, dw_b, ln2_w, ln2_b, eps2,
+                           fc_bf16x2, fc_b, xh, stats, n2_w, n2_b, branch_scale, out, B, D, H, W);
+    switch (plan.back) {
+      case FFN_BACK_FUSED:
+        d.pw = pw_bf16x2;
+        d.pw_b = pw_b;
+        d.ln1_w = ln1_w;
+        d.ln1_b = ln1_b;
+        d.eps1 = eps1;
+        return launch_ffn_fused(d, precision, s);
+      case FFN_BACK_DWFC_TB4: return launch_ffn_dwfc_tb4(d, precision, s);
+      case FFN_BACK_DWFC_SB: return launch_ffn_dwfc_sb(d, precision, s);
+      case FFN_BACK_DWFC2_TB: return launch_ffn_dwfc2(d, precision, true, s);
+      case FFN_BACK_DWFC2_KERNEL: return launch_ffn_dwfc2(d, precision, false, s);
+      default:  // FFN_BACK_DWFC3_TB
+        d.fcs = reinterpret_cast<uint16_t*>(base + ws.fcs);
+        return launch_ffn_dwfc3(d, precision, s);
+    }
   }
-  const bool split_ln = hidden % 32 == 0;
-  WF_REQUIRE(!keep || split_ln, "training needs hidden % 32 == 0 (h2 kept pre-LayerNorm)");
-  float* pst = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + 2 * one);
-  if (stage == 0 || stage == 2) {
-    if (split_ln && split_ln1 && pw_np > 0)  // LN1 + GELU in the staging
-      rc = launch_dwconv3d(h1, dw_w, dw_b, h2, pst, (int)B, (int)hidden, (int)D, (int)H,
-                           (int)W, precision, s, nullptr, ln1_st, ln1_w, ln1_b);
-    else if (split_ln)
-      rc = launch_dwconv3d(h1, dw_w, dw_b, h2, pst, (int)B, (int)hidden, (int)D, (int)H,
-                           (int)W, precision, s);
+  // ---- back, staged: the depthwise conv into h2, then the fc GEMM
+  const bool ln2_loader = plan.back == FFN_BACK_STAGED;
+  if (run_dw) {
+    if (ln2_loader)  // LN1 + GELU in the staging where the front left them to it
+      rc = launch_dwconv3d(h1, dw_w, dw_b, h2, ln2_pst, (int)B, (int)hidden, (int)D, (int)H, (int)W,
+                           precision, s, nullptr,
+                           plan.front == FFN_FRONT_PARTIALS ? ln1_st : nullptr, ln1_w, ln1_b);
     else
       rc = launch_dwconv_ln_gelu(h1, dw_w, dw_b, ln2_w, ln2_b, eps2, h2, (int)B, (int)hidden,
                                  (int)D, (int)H, (int)W, precision, s);
   }
-  if (rc || stage == 1 || stage == 2) return rc;
-  GemmArgs f{};
-  f.prec = precision;
-  f.a_src = h2;
-  f.a_bf16 = hbf;
-  f.a_C = (int)hidden;
-  f.a_nseg = 1;
-  f.a_map = MAP_IDENTITY;
-  if (split_ln) {
-    f.a_ln = LN_PARTIAL;
-    f.a_stats = pst;
-    f.a_np = (int)(hidden / DW_STAT_GROUP);
-    f.a_ln_w = ln2_w;
-    f.a_ln_b = ln2_b;
-    f.a_eps = eps2;
-    f.a_gelu = 1;
-  } else {
-    f.a_ln = LN_NONE;
-  }
-  f.w = fc_bf16x2;
-  f.M = M;
-  f.N = (int)C;
-  f.K = (int)hidden;
-  f.epi = EPI_RESID;
-  f.bias = fc_b;
-  f.r_x = xh;
-  f.r_stats = stats;
-  f.r_ln_w = n2_w;
-  f.r_ln_b = n2_b;
-  f.r_scale = branch_scale;
-  f.rows_per_sample = D * H * W;
-  f.out = out;
-  f.out_bf16 = 0;
-  f.ldo = C;
-  if (!keep) {  // h1 is dead once the depthwise conv has read it: the fc's split-K scratch
+  if (rc || !run_fc) return rc;
+  GemmArgs f = fc_gemm_args(h2, ln2_loader ? ln2_pst : nullptr, ln2_w, ln2_b, eps2, fc_bf16x2, fc_b,
+                            xh, stats, n2_w, n2_b, branch_scale, out, M, C, hidden, D * H * W,
+                            precision);
+  if (!train) {  // h1 is dead once the depthwise conv has read it: the fc's split-K scratch
     f.kpart = reinterpret_cast<float*>(h1);
-    f.kpart_bytes = one;
+    f.kpart_bytes = ws.h2 - ws.h1;
   }
   return launch_gemm(f, s, "wf_ccf_ffn_fwd(fc)");
 }

@@ -17,6 +17,7 @@
 // (ffn_dwfc_tb.hip); ffn_dwfc_sb below serves PREC_BF16 and outputs of 2 GiB and above.
 // Likewise for the stage-2 shape (C = 96, hidden = 384): the default is ffn_dwfc2_tb
 // (ffn_dwfc2_tb.hip); ffn_dwfc2_kernel below serves PREC_BF16 and tensors of 2 GiB and above.
+// Both choices are made by ffn_plan (ffn_plan.hpp), not here.
 #include "ffn_dwfc_common.hpp"
 
 namespace wf {
@@ -704,7 +705,7 @@ __global__ __launch_bounds__(768, 1) void ffn_dwfc2_kernel(DwFcArgs a) {
   PROBE_DUMP
 }
 
-int launch_ffn_dwfc2(const DwFcArgs& a, int prec, hipStream_t s) {
+int launch_ffn_dwfc2(const DwFcArgs& a, int prec, bool tb, hipStream_t s) {
   typedef DwFc2 K;
   DwFcArgs g = a;
   // z segment: whole columns where that still gives two workgroups per CU (B = 8 at 32^3:
@@ -716,8 +717,8 @@ int launch_ffn_dwfc2(const DwFcArgs& a, int prec, hipStream_t s) {
   g.dbg = ffn_dbg_env();
   // ffn_dwfc2_tb reads fp32 h1 and addresses x, out and the h1 plane through 32-bit buffer
   // offsets (2 GiB): bf16 h1 and larger tensors (stage 2 of a 128^3 input at B >= 171) keep
-  // ffn_dwfc2_kernel, which has no such limit
-  if (prec != PREC_BF16 && ffn_dwfc2_tb_fits(g)) return launch_ffn_dwfc2_tb(g, prec, s);
+  // ffn_dwfc2_kernel, which has no such limit (ffn_plan)
+  if (tb) return launch_ffn_dwfc2_tb(g, prec, s);
   const int64_t blocks = base * cdiv(g.D, ZS);
   void (*kern)(DwFcArgs) = prec == PREC_SPLIT  ? ffn_dwfc2_kernel<PREC_SPLIT, float>
                            : prec == PREC_FP16 ? ffn_dwfc2_kernel<PREC_FP16, float>
@@ -727,8 +728,11 @@ int launch_ffn_dwfc2(const DwFcArgs& a, int prec, hipStream_t s) {
   return check_launch("ffn_dwfc2");
 }
 
-// 4 x 8 tiles: 12 waves and ~154 KB of LDS, one workgroup per CU
-static int launch_ffn_dwfc_sb(const DwFcArgs& a, int prec, hipStream_t s) {
+// 4 x 8 tiles: 12 waves and ~154 KB of LDS, one workgroup per CU.  The plan (ffn_plan) sends
+// bf16 h1 and tensors beyond ffn_dwfc_tb4's 32-bit buffer offsets here (stage 1 of a 128^3
+// input at B >= 43, or one plane of 1673 x 1673 positions); fp32 h1 below that takes
+// ffn_dwfc_tb4 (977-989 vs 1027-1043 us for this kernel at B = 8, profiles/r4_ffn_tb/)
+int launch_ffn_dwfc_sb(const DwFcArgs& a, int prec, hipStream_t s) {
   constexpr int C = 48, HID = 192, TY = 4, TX = 8;
   typedef DwFcCfg<C, HID, TY, TX> K;
   DwFcArgs g = a;
@@ -749,15 +753,6 @@ static int launch_ffn_dwfc_sb(const DwFcArgs& a, int prec, hipStream_t s) {
   set_max_lds(reinterpret_cast<const void*>(kern), (int)lds);
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(K::NTH), lds, s, g);
   return check_launch("ffn_dwfc_sb");
-}
-
-int launch_ffn_dwfc_s1(const DwFcArgs& a, int prec, hipStream_t s) {
-  // ffn_dwfc_tb4 reads fp32 h1 (977-989 vs 1027-1043 us for ffn_dwfc_sb at B = 8,
-  // profiles/r4_ffn_tb/) and addresses x, out and one h1 plane through 32-bit buffer offsets
-  // (2 GiB): bf16 h1 and larger tensors (stage 1 of a 128^3 input at B >= 43, or one plane of
-  // 1673 x 1673 positions) take the SIMD-balanced kernel, which has no such limit
-  return prec != PREC_BF16 && ffn_dwfc_tb4_fits(a) ? launch_ffn_dwfc_tb4(a, prec, s)
-                                                   : launch_ffn_dwfc_sb(a, prec, s);
 }
 
 }  // namespace wf

@@ -432,7 +432,7 @@ __global__ __launch_bounds__(1024, 1) void ffn_dwfc2_tb_kernel(DwFcArgs a) {
 int launch_ffn_dwfc2_tb(const DwFcArgs& g, int prec, hipStream_t s) {
   using namespace tb2;
   if (prec != PREC_SPLIT && prec != PREC_FP16) return fail(WF_E_SHAPE, "ffn_dwfc2_tb: fp32 h1 only");
-  if (!ffn_dwfc2_tb_fits(g))
+  if (!ffn_dwfc2_tb_fits(g.B, g.D, g.H, g.W))
     return fail(WF_E_SHAPE, "ffn_dwfc2_tb: tensor beyond the 2 GiB buffer-offset range");
   const int64_t blocks =
       (int64_t)g.B * cdiv(g.H, TY) * cdiv(g.W, TX) * cdiv(g.D, g.ZS);

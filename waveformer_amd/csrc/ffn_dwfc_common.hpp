@@ -37,12 +37,10 @@ struct DwFcArgs {
   const float* ln1_b;
   float eps1;
   int dbg;               // timing experiments only (builds with WF_FFN_DBG=1): phases skipped
-  // ffn_dwfc3_tb only: DWFC3_FCS_BYTES of workspace for the fc weight in stream order
+  // ffn_dwfc3_tb only: DWFC3_FCS_BYTES of workspace (FfnWorkspace::fcs, ffn_plan.hpp) for the
+  // fc weight in stream order
   uint16_t* fcs;
 };
-// the stage-3 fc weight (192 x 768 bf16 hi + lo) rewritten per call as the 1-KB fragments the E
-// waves of ffn_dwfc3_tb stream: the tail of wf_ccf_ffn_workspace_bytes at that shape
-constexpr int64_t DWFC3_FCS_BYTES = 2 * 192 * 768 * 2;
 #ifndef WF_FFN_DBG  // 1: timing-experiment build (DwFcArgs::dbg phase skips; never the shipped library)
 #define WF_FFN_DBG 0
 #endif
@@ -52,41 +50,27 @@ inline int ffn_dbg_env() {
   return WF_FFN_DBG && getenv("WF_FFN_DBG") ? atoi(getenv("WF_FFN_DBG")) : 0;
 }
 
-// ---- launchers
-// stage-1 shape: ffn_dwfc_tb4 for fp32 h1 where ffn_dwfc_tb4_fits, else ffn_dwfc_sb
-int launch_ffn_dwfc_s1(const DwFcArgs& a, int prec, hipStream_t s);
-// three VALU waves per SIMD on 4 x 8 tiles, two barriers per plane (ffn_dwfc_tb.hip)
+// ---- launchers.  Which of them a call takes is ffn_plan's decision (ffn_plan.hpp, FfnBack):
+// the tb kernels read fp32 h1 within their 32-bit offsets (ffn_dwfc*_tb_fits, there), and
+// their launchers refuse anything else.
+// stage-1 shape, three VALU waves per SIMD on 4 x 8 tiles, two barriers per plane
+// (ffn_dwfc_tb.hip)
 int launch_ffn_dwfc_tb4(const DwFcArgs& a, int prec, hipStream_t s);
-// the same for C = 96, hidden = 384 (4 x 4 tiles, depthwise inputs loaded straight into
-// registers, two h2 tiles and the fc weight hi in LDS):
-// ffn_dwfc2_tb for fp32 h1 where ffn_dwfc2_tb_fits, else ffn_dwfc2_kernel; sets ZS
-int launch_ffn_dwfc2(const DwFcArgs& a, int prec, hipStream_t s);
-// three depthwise waves + one fc wave per SIMD (ffn_dwfc2_tb.hip); ZS set by the caller
+// stage-1 shape, SIMD-balanced roles (ffn_dwfc.hip): any precision, no size limit
+int launch_ffn_dwfc_sb(const DwFcArgs& a, int prec, hipStream_t s);
+// C = 96, hidden = 384 on 4 x 4 tiles; picks ZS.  tb: ffn_dwfc2_tb (three depthwise waves + one
+// fc wave per SIMD, depthwise inputs loaded straight into registers, two h2 tiles and the fc
+// weight hi in LDS), else ffn_dwfc2_kernel (any precision, no size limit)
+int launch_ffn_dwfc2(const DwFcArgs& a, int prec, bool tb, hipStream_t s);
+// ffn_dwfc2_tb.hip; ZS set by the caller
 int launch_ffn_dwfc2_tb(const DwFcArgs& a, int prec, hipStream_t s);
 // the stage-3 shape, C = 192, hidden = 768, fp32 h1 (ffn_dwfc3_tb.hip): 4 x 4 tiles, direct
 // depthwise loads, three h2 tiles in LDS, the fc weight streamed from L2 into registers; sets
-// ZS.  Only where ffn_dwfc3_tb_fits: the caller keeps the staged path for the rest
+// ZS.  Only where ffn_dwfc3_tb_fits: the plan keeps the staged path for the rest
 int launch_ffn_dwfc3(const DwFcArgs& a, int prec, hipStream_t s);
 // ---- the whole CCF_FFN + norm2 + Q4 residual in one kernel for C = 48, hidden = 192: the
 // haloed h1 plane is computed in LDS from the x rows (pw MFMA + LN1 + GELU), never stored
 int launch_ffn_fused(const DwFcArgs& a, int prec, hipStream_t s);
-// The tb kernels address x, out and one h1 plane through 32-bit buffer byte offsets, and mark
-// halo positions outside the volume with the offset BUF_OOR = 2^31, which must lie beyond the
-// plane descriptor's range: x / out (C channels) and one haloed plane (HID channels) stay
-// below 2 GiB.  (ffn_dwfc2_tb's D waves load the plane directly through such a descriptor and
-// mark "outside" with a descriptor range of 0 instead.)  Larger shapes take ffn_dwfc_sb /
-// ffn_dwfc2_kernel, which have no such limit.
-inline bool ffn_dwfc_tb4_fits(const DwFcArgs& a) {
-  return (int64_t)a.B * a.D * a.H * a.W * 48 * 4 < ((int64_t)1 << 31) &&
-         (int64_t)a.H * a.W * 192 * 4 < ((int64_t)1 << 31);
-}
-inline bool ffn_dwfc2_tb_fits(const DwFcArgs& a) {
-  return (int64_t)a.B * a.D * a.H * a.W * 96 * 4 < ((int64_t)1 << 31) &&
-         ((int64_t)a.H * a.W + 8) * 384 * 4 < ((int64_t)1 << 31);
-}
-inline bool ffn_dwfc3_tb_fits(int64_t B, int64_t D, int64_t H, int64_t W) {
-  return B * D * H * W * 192 * 4 < ((int64_t)1 << 31) && (H * W + 8) * 768 * 4 < ((int64_t)1 << 31);
-}
 
 // h1 plane staging: fp32 (SPLIT / FP16 workspaces) or bf16 (BF16) rows widened to fp32
 template <typename T>

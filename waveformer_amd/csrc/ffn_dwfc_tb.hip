@@ -468,7 +468,7 @@ int launch_ffn_dwfc_tb4(const DwFcArgs& a, int prec, hipStream_t s) {
   g.dbg = ffn_dbg_env();
   const int64_t blocks = base * cdiv(g.D, g.ZS);
   if (prec != PREC_SPLIT && prec != PREC_FP16) return fail(WF_E_SHAPE, "ffn_dwfc_tb4: fp32 h1 only");
-  if (!ffn_dwfc_tb4_fits(g))
+  if (!ffn_dwfc_tb4_fits(g.B, g.D, g.H, g.W))
     return fail(WF_E_SHAPE, "ffn_dwfc_tb4: tensor beyond the 2 GiB buffer-offset range");
   void (*kern)(DwFcArgs) = prec == PREC_SPLIT ? ffn_dwfc_tb4_kernel<PREC_SPLIT>
                                               : ffn_dwfc_tb4_kernel<PREC_FP16>;

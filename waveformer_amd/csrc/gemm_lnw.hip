@@ -192,7 +192,7 @@ void go_lnw(const GemmArgs& g, hipStream_t s) {
 // against 61.6 + 43.9 for gemm_kc + ln_act_fwd at B = 8 (profiles/r5_lnw_wide_ab.txt).  The
 // stage-4 N = 1536 on 16 waves measured 81.9 against 29.3 + 21.2 (256 workgroups of 16 rows
 // each streaming the 2.4 MB weight: latency-bound), so it stays on the split path
-bool gemm_lnw_wide_shape(const GemmArgs& g) { return g.N == 768 && (g.K + 31) / 32 == 6; }
+// (gemm_lnw_wide_shape, ffn_plan.hpp: the CCF_FFN plan uses the same predicate)
 
 int try_launch_gemm_lnw(const GemmArgs& g, hipStream_t s) {
   if (g.epi != EPI_LN_GELU || g.a_map != MAP_IDENTITY || g.a_bf16 || g.a_gelu ||

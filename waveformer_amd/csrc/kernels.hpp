@@ -1,5 +1,6 @@
 // kernels.hpp -- internal launchers shared by the C-ABI translation units.
 #pragma once
+#include "ffn_plan.hpp"
 #include "wf_common.hpp"
 
 namespace wf {
@@ -201,7 +202,8 @@ int launch_dwconv_ln_gelu(const void* in, const float* w, const float* b, const 
                           int W, int prec, hipStream_t s);
 // ---- depthwise 3^3 conv + bias only (the LayerNorm + GELU run in the next GEMM's loader);
 // returns 0 on success, WF_E_SHAPE if the shape is not covered (Hd % 32 != 0)
-// pstats (optional): (M, Hd / 32, 2) {mean, M2} of each 32-channel group of every output row
+// pstats (optional): (M, Hd / 32, 2) {mean, M2} of each 32-channel group (DW_STAT_GROUP,
+// ffn_plan.hpp) of every output row
 // cstats (optional): zeroed (B, Hd, 2) fp64 {sum, sum of squares} of the outputs per channel
 int launch_dwconv3d(const void* in, const float* w, const float* b, void* out, float* pstats,
                     int B, int Hd, int D, int H, int W, int prec, hipStream_t s,
@@ -210,7 +212,6 @@ int launch_dwconv3d(const void* in, const float* w, const float* b, void* out, f
 // per-row {mean, rstd} from np equal-size {mean, M2} partials (Chan et al.), (M, 2)
 int launch_ln_stats_finalize(const float* pstats, int np, int group, float eps, float* out,
                              int64_t M, hipStream_t s);
-constexpr int DW_STAT_GROUP = 32;
 // ---- the CCF_FFN back-half kernels (DwFcArgs, launch_ffn_*): ffn_dwfc_common.hpp, below
 // K-chunked MFMA GEMM (gemm_kc.hip) for the shapes whose weight does not fit gemm_rows' LDS
 // in one column chunk; returns 1 if it took the shape
@@ -224,8 +225,8 @@ int try_launch_pw2_resident(const GemmArgs& g, hipStream_t s);
 // stage-2 CCF_FFN pwconv (N = 384 with the LayerNorm + GELU epilogue, gemm_lnw.hip): columns
 // split over the waves; returns 1 if it took the shape
 int try_launch_gemm_lnw(const GemmArgs& g, hipStream_t s);
-// the stage-3/4 wide-row pwconv shapes gemm_lnw takes (LayerNorm + GELU epilogue)
-bool gemm_lnw_wide_shape(const GemmArgs& g);
+// the stage-3/4 wide-row pwconv shapes gemm_lnw takes (LayerNorm + GELU epilogue): ffn_plan.hpp
+inline bool gemm_lnw_wide_shape(const GemmArgs& g) { return gemm_lnw_wide_shape(g.N, g.K); }
 
 }  // namespace wf
 

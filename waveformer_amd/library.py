@@ -61,10 +61,21 @@ def ffn_workspace_bytes(B, C, hidden, D, H, W):
     """wf_ccf_ffn_workspace_bytes(..., WF_PREC_BF16X3): h1 and h2 fp32 + the dwconv's
     (mean, M2) per 32 channels of every position + the same-size area of the pwconv's LN1
     partials + their per-row (mean, rstd) (ffn.hip, WF_FFN_LN1_FUSE) + at the stage-3 shape the
-    fc weight in the order ffn_dwfc3_tb streams it."""
+    fc weight in the order ffn_dwfc3_tb streams it.  The only restatement of ffn_workspace
+    (csrc/ffn_plan.hpp) in Python, for fake tensors; real calls ask _ffn_offsets."""
     M = B * D * H * W
     return (2 * _round256(M * hidden * 4) + 2 * _round256(M * (hidden // 32) * 2 * 4)
             + _round256(M * 2 * 4) + (2 * 192 * 768 * 2 if (C, hidden) == (192, 768) else 0))
+
+
+def _ffn_offsets(B, C, hidden, D, H, W):
+    """The training call's workspace layout (wf_ccf_ffn_plan, bf16x3): byte offsets of h1, h2,
+    the LN2 partials, the LN1 partials, the LN1 row statistics, the stage-3 fc stream area (-1:
+    none) and the total."""
+    off = (ctypes.c_int64 * 7)()
+    if _lib.query("wf_ccf_ffn_plan", B, C, hidden, D, H, W, SPLIT, 1, off) < 0:
+        raise RuntimeError(_lib.load().wf_last_error().decode(errors="replace"))
+    return list(off)
 
 
 # ------------------------------------------------------------------------------------------
@@ -581,13 +592,12 @@ def ccf_ffn(xh: Tensor, stats: Optional[Tensor], n2w: Optional[Tensor], n2b: Opt
     pw = ops.split_weight(pww, (hid, C), SPLIT)
     fc = ops.split_weight(fcw, prec=SPLIT)
     out = torch.empty_like(xh)
-    wsb = _lib.query("wf_ccf_ffn_workspace_bytes", B, C, hid, D, H, W, SPLIT)
-    work = torch.empty(wsb, dtype=torch.uint8, device=xh.device)
-    # the training path writes h1, h2 and the LN2 partials; the inference-only LN1 areas after
-    # them are zeroed so the returned workspace is a deterministic function of the inputs
-    M = B * D * H * W
-    used = 2 * _round256(M * hid * 4) + _round256(M * (hid // 32) * 2 * 4)
-    work[used:].zero_()
+    off = _ffn_offsets(B, C, hid, D, H, W)
+    work = torch.empty(off[6], dtype=torch.uint8, device=xh.device)
+    # the training path writes h1, h2 and the LN2 partials; the inference-only areas after them
+    # (from the LN1 partials on) are zeroed so the returned workspace is a deterministic
+    # function of the inputs
+    work[off[3]:].zero_()
     _lib.call("wf_ccf_ffn_stage", _FFN_KEEP, xh.data_ptr(), _p(stats), _p(n2w), _p(n2b),
               pw.data_ptr(), _p(pwb), l1w.data_ptr(), l1b.data_ptr(), float(eps1),
               dww.data_ptr(), dwb.data_ptr(), l2w.data_ptr(), l2b.data_ptr(), float(eps2),
@@ -637,9 +647,9 @@ def ccf_ffn_backward(gout: Tensor, xh: Tensor, n2w: Optional[Tensor], n2b: Optio
     hid = pww.shape[0]
     M = B * D * H * W
     E = lambda: _empty(xh, torch.float32)  # noqa: E731  (outputs may not alias)
-    one = (M * hid * 4 + 255) & ~255
-    u1 = work[:M * hid * 4].view(torch.float32).view(M, hid)           # GELU(LN1(pw))
-    h2 = work[one:one + M * hid * 4].view(torch.float32).view(M, hid)  # dwconv + bias
+    off = _ffn_offsets(B, C, hid, D, H, W)
+    u1 = work[off[0]:off[0] + M * hid * 4].view(torch.float32).view(M, hid)  # GELU(LN1(pw))
+    h2 = work[off[1]:off[1] + M * hid * 4].view(torch.float32).view(M, hid)  # dwconv + bias
     g = _f32(gout).view(M, C)
     x2 = xh.view(M, C)
     df = _scale_rows(g.view(B, -1), s_mlp).view(M, C) if block else g
