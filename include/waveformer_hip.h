@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define WF_ABI_VERSION 26
+#define WF_ABI_VERSION 27
 
 enum { WF_PREC_BF16 = 0, WF_PREC_BF16X3 = 1, WF_PREC_FP16 = 2 };
 
@@ -975,6 +975,38 @@ int wf_augment_pointwise(float* x, int64_t N, int64_t S, int op, const double* p
                          void* workspace, int64_t workspace_bytes, void* stream);
 int wf_channel_stats(const float* x, int64_t N, int64_t S, double* stats, void* workspace,
                      int64_t workspace_bytes, void* stream);
+
+/* ======================================================================================
+ * Resampling (ABI 27): the resampling step of preprocessing, the 3-D branch of
+ * light_training/preprocessing/resampling/default_resampling.py resample_data_or_seg.  Same
+ * rules as above: no launch reads what another workgroup writes, no atomics, bitwise
+ * repeatable.
+ * ====================================================================================== */
+
+/* One axis (0 = D, 1 = H, 2 = W) of zoom(order=3, mode='nearest', grid_mode=True), i.e. of
+ * skimage.transform.resize(order=3, mode='edge', anti_aliasing=False), on N fp32 planes
+ * (D, H, W): the cubic prefilter over the edge-padded line (the 18 + 18 taps of
+ * wf_spline_prefilter_axis(EDGE)) and the 4-tap interpolation at (o + 0.5) n / on - 0.5 + 12,
+ * fused.  out holds N planes whose `axis` length is on.  The zoom is axis aligned, so the three
+ * axes in any order are the 3-D zoom.  clip: NULL, or the (N, 4) device fp64 rows {mean, std,
+ * min, max} of wf_channel_stats: plane n's outputs are clamped to its [min, max] (resize's
+ * clip=True; pass it with the last axis only).  in != out.                                  */
+int wf_spline_zoom_axis(const float* in, float* out, int64_t N, int64_t D, int64_t H, int64_t W,
+                        int axis, int64_t on, const double* clip, void* stream);
+
+/* Host only: how wf_spline_zoom_axis cuts an axis n -> on into segments of outputs, each staged
+ * by one workgroup.  Returns the number of segments, or a negative status.  With plan (8 host
+ * int64) it describes segment seg: {o0, o1, jlo, jhi, slo, shi, coefficient capacity, sample
+ * capacity}: the outputs [o0, o1), the coefficients [jlo, jhi] of the padded line of n + 24
+ * their taps span, and the input samples [slo, shi] those coefficients read.                */
+int wf_spline_zoom_axis_plan(int64_t n, int64_t on, int64_t seg, int64_t* plan);
+
+/* batchgenerators' resize_segmentation(order=1) of int16 labels (D, H, W) to (oD, oH, oW): per
+ * output voxel zoom(order=1)'s coordinate (o + 0.5) n / on - 0.5 clamped to [0, n - 1], the taps
+ * floor and floor + 1 (clamped), weights in fp64 summed per distinct label among the eight taps;
+ * the largest label whose sum is >= 0.5 wins, else 0.  One pass, no per-label volumes.      */
+int wf_zoom_seg_linear(const int16_t* seg, int64_t D, int64_t H, int64_t W, int64_t oD,
+                       int64_t oH, int64_t oW, int16_t* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -8,6 +8,14 @@ read-backs), and (b) the whole run_case_npy with the volumes already on the devi
 around it.  It also prints the number of fill rounds the case needs and, where scipy is
 importable, the time of the numpy / scipy restatement (tests/preprocess_ref.py) on this host's
 CPU.  The process ends itself after --limit seconds.  --out FILE also writes the lines there.
+
+--resample-out FILE adds the resample stage on the cropped, z-scored data: spacing 1 mm -> 1.5 mm
+(down) and -> 0.75 mm (up).  In each direction it alternates the fused path
+(ops.zoom_cubic_volume: channel_stats and one launch per axis) with the composition of the older
+entry points (spline_prefilter(EDGE) on the three axes, zoom_cubic on the padded coefficients,
+a clamp to the channels' ranges), times the segmentation resize, and writes the times with the
+bytes each path moves (computed from the shapes) and their share of the HBM peak of 8.0 TB/s.
+--errors-out FILE writes the largest difference between the two paths at that size.
 Reported, not gated."""
 import argparse
 import os
@@ -68,6 +76,97 @@ def line(name, ms):
             f"max {max(ms):9.3f}   ({len(ms)} repeats)")
 
 
+HBM_PEAK = 8.0e12  # bytes / s, the MI355X's specified peak
+
+
+def composed_zoom(x, size, lo, hi):
+    """The composition the older entry points offer: three padded prefilter passes, the 64-tap
+    zoom, and the clamp to the channels' [min, max] (lo, hi: (N, 1, 1, 1))."""
+    coef = ops.spline_prefilter(x, ops.SPLINE_EDGE)
+    return torch.minimum(torch.maximum(ops.zoom_cubic(coef, size), lo), hi)
+
+
+def zoom_bytes(shape, size):
+    """fp32 bytes (read + written) of the two paths for N planes shape -> size: (fused, composed)."""
+    n = shape[0]
+    vox = lambda d: n * d[0] * d[1] * d[2] * 4  # noqa: E731
+    cur, fused = list(shape[1:]), vox(shape[1:])  # channel_stats reads the input once
+    for a in range(3):
+        if cur[a] == size[a]:
+            continue
+        nxt = list(cur)
+        nxt[a] = size[a]
+        fused += vox(cur) + vox(nxt)
+        cur = nxt
+    cur, comp = list(shape[1:]), 2 * vox(shape[1:])  # amin and amax read the input twice
+    for a in range(3):
+        nxt = list(cur)
+        nxt[a] += 2 * ops.SPLINE_PAD
+        comp += vox(cur) + vox(nxt)
+        cur = nxt
+    comp += vox(cur) + vox(size)  # the gather reads every coefficient at least once
+    comp += 4 * vox(size)         # maximum and minimum: a read and a write each
+    return fused, comp
+
+
+def resample_stage(norm, seg16, w, n):
+    """norm (C, d, h, w) fp32 z-scored, seg16 (d, h, w) int16, both cropped.  Returns (time
+    lines, error lines)."""
+    from waveformer_amd import resampling
+    shape = tuple(int(v) for v in norm.shape)
+    lines, errs = [], []
+    lo = norm.amin(dim=(1, 2, 3), keepdim=True)
+    hi = norm.amax(dim=(1, 2, 3), keepdim=True)
+    for name, spacing in (("down, 1 mm -> 1.5 mm", 1.5), ("up, 1 mm -> 0.75 mm", 0.75)):
+        size = tuple(int(v) for v in resampling.compute_new_shape(shape[1:], (1.0,) * 3,
+                                                                  (spacing,) * 3))
+        fused = lambda: ops.zoom_cubic_volume(norm, size, clip=True)  # noqa: E731
+        comp = lambda: composed_zoom(norm, size, norm.amin(dim=(1, 2, 3), keepdim=True),  # noqa: E731
+                                     norm.amax(dim=(1, 2, 3), keepdim=True))
+        for _ in range(w):
+            fused(), comp()
+        t_f, t_c = [], []
+        for _ in range(n):  # alternate the two paths
+            t_f += timed(fused, 0, 1)
+            t_c += timed(comp, 0, 1)
+        t_s = timed(lambda: ops.zoom_seg_linear(seg16, size), w, n)
+        b_f, b_c = zoom_bytes(shape, size)
+        lines.append(f"{name}: {shape} -> {size}")
+        for label, ms, nbytes in (("fused (stats + 3 axis passes)", t_f, b_f),
+                                  ("composed (3 prefilters + zoom + clamp)", t_c, b_c)):
+            med = statistics.median(ms) * 1e-3
+            lines.append(line("  " + label, ms))
+            lines.append(f"    bytes moved (from the shapes) {nbytes / 1e6:9.1f} MB = "
+                         f"{nbytes / med / 1e9:8.1f} GB/s = {100 * nbytes / med / HBM_PEAK:5.2f} % "
+                         f"of the HBM peak of {HBM_PEAK / 1e12:.1f} TB/s")
+        lines.append(line("  zoom_seg_linear", t_s))
+        a, b = fused(), composed_zoom(norm, size, lo, hi)
+        diff = (a - b).abs()
+        # both paths are within 95 * 2^-23 * cmax of float64 (tests/test_gpu_resample.py), cmax at
+        # least the largest input magnitude: they may differ by twice that
+        allowed = 2 * 95 * 2.0 ** -23 * norm.abs().max().item()
+        errs.append(f"{name}: {shape} -> {size}: max |fused - composed| {diff.max().item():.3e} "
+                    f"(max |value| {b.abs().max().item():.3e}; twice the tests' bound is at least "
+                    f"{allowed:.3e}); differing elements {int((diff > 0).sum())} of {diff.numel()}")
+        del a, b, diff
+    return lines, errs
+
+
+def cpu_resample(norm_h, seg_h):
+    """The numpy / scipy restatement (tests/resample_ref.py) of the down direction, one run."""
+    from tests import resample_ref as ref
+    from waveformer_amd import resampling
+    size = tuple(int(v) for v in resampling.compute_new_shape(norm_h.shape[1:], (1.0,) * 3,
+                                                              (1.5,) * 3))
+    t = time.perf_counter()
+    ref.resample_data_or_seg(norm_h, size)
+    t_d = time.perf_counter() - t
+    t = time.perf_counter()
+    ref.resample_data_or_seg(seg_h[None], size, is_seg=True, order=1)
+    return [(f"resize of {norm_h.shape[0]} channels -> {size}", t_d),
+            ("resize_segmentation (order 1)", time.perf_counter() - t)]
+
+
 def cpu_restatement(data, seg):
     """The numpy / scipy restatement of the same case, stage by stage, one run."""
     from tests import preprocess_ref as ref
@@ -93,12 +192,21 @@ def cpu_restatement(data, seg):
     return out
 
 
+def write(path, text):
+    if path:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=9)
     ap.add_argument("--limit", type=int, default=300, help="seconds after which the process ends")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--resample-out", default=None, help="time the resample stage, write it here")
+    ap.add_argument("--errors-out", default=None, help="fused against composed resample, here")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("kbench_preprocess: needs a GPU")
@@ -152,10 +260,23 @@ def main():
         out.append("scipy is not importable here: no CPU restatement timed")
     text = "\n".join(out)
     print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    write(args.out, text)
+
+    if args.resample_out or args.errors_out:
+        norm = ops.crop_normalize(data, bbox, stats)
+        head = [f"resampling of the cropped, z-scored case, {torch.cuda.get_device_name(0)}"]
+        lines, errs = resample_stage(norm, cropped_seg, w, n)
+        try:
+            import scipy  # noqa: F401
+            cpu = cpu_resample(norm.cpu().numpy(), cropped_seg.cpu().numpy())
+            lines.append(f"numpy / scipy {scipy.__version__} restatement on this host's CPU, "
+                         "down direction, one run:")
+            lines += [f"  {name:<46s} {sec * 1e3:9.1f} ms" for name, sec in cpu]
+        except ImportError:
+            lines.append("scipy is not importable here: no CPU restatement timed")
+        print("\n".join(head + lines + errs))
+        write(args.resample_out, "\n".join(head + lines))
+        write(args.errors_out, "\n".join(head + errs))
 
 
 if __name__ == "__main__":

@@ -173,9 +173,13 @@ SIGNATURES = {
     "wf_augment_pointwise_workspace_bytes": (_I64, [_I64, _I64]),
     "wf_augment_pointwise": (_I, [_P, _I64, _I64, _I, _P, _P, _P, _P, _P, _I64, _P]),
     "wf_channel_stats": (_I, [_P, _I64, _I64, _P, _P, _I64, _P]),
+    # resampling (fused cubic zoom per axis, per-label linear zoom of the segmentation)
+    "wf_spline_zoom_axis": (_I, [_P, _P, _I64, _I64, _I64, _I64, _I, _I64, _P, _P]),
+    "wf_spline_zoom_axis_plan": (_I, [_I64, _I64, _I64, _P]),
+    "wf_zoom_seg_linear": (_I, [_P] + [_I64] * 6 + [_P, _P]),
 }
 
-ABI_VERSION = 26
+ABI_VERSION = 27
 _lock = threading.Lock()
 _lib = None
 _err = None

@@ -20,49 +20,14 @@
 #include <algorithm>
 #include <math.h>
 
+#include "spline.hpp"
 #include "wf_common.hpp"
 
 namespace wf {
 
-constexpr int AUG_MAX_R = 20;         // taps on either side of a FIR centre
-constexpr int AUG_SPLINE_TAPS = 18;   // the cut leaves 2 sqrt(3) |p|^19 / (1 - |p|) = 6.4e-11 max|x|
-constexpr int AUG_PAD = WF_SPLINE_PAD;
 constexpr int AUG_MAX_C = 64;
 constexpr int AUG_STAT_BLOCKS = 256;  // upper bound of statistic partials per plane
 constexpr int AUG_PART = 6;           // doubles per partial: n, shift, sum, sum of squares, min, max
-
-struct FirTaps {
-  float w[AUG_MAX_R + 1];
-  int r;
-};
-
-enum { FIR_MIRROR = 0, FIR_REFLECT = 1, FIR_EDGEPAD = 2 };
-
-// whole-sample mirror of any index onto [0, n): ... 2 1 | 0 1 2 ... n-1 | n-2 ...
-__device__ __forceinline__ int mirror_index(int j, int n) {
-  if ((unsigned)j < (unsigned)n) return j;
-  if (n == 1) return 0;
-  const int P = 2 * (n - 1);
-  int m = j % P;
-  if (m < 0) m += P;
-  return m < n ? m : P - m;
-}
-
-// half-sample mirror (scipy's `reflect`): ... 1 0 | 0 1 ... n-1 | n-1 n-2 ...
-__device__ __forceinline__ int reflect_index(int j, int n) {
-  if ((unsigned)j < (unsigned)n) return j;
-  const int P = 2 * n;
-  int m = j % P;
-  if (m < 0) m += P;
-  return m < n ? m : P - 1 - m;
-}
-
-template <int MODE>
-__device__ __forceinline__ int fir_src(int j, int n_in, int n_out) {
-  if (MODE == FIR_REFLECT) return reflect_index(j, n_in);
-  if (MODE == FIR_MIRROR) return mirror_index(j, n_in);
-  return min(max(mirror_index(j, n_out) - AUG_PAD, 0), n_in - 1);
-}
 
 // out (outer, n_out, inner) = FIR along the middle axis of in (outer, n_in, inner); the taps are
 // added from the outermost pair inwards, smallest first
@@ -88,25 +53,8 @@ __global__ __launch_bounds__(256) void fir_axis_kernel(const float* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------
-// cubic evaluation: scipy's order-3 weights and the 64 taps, x innermost
+// cubic evaluation: the 64 taps, x innermost (weights and tap indices: spline.hpp)
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ void cubic_weights(float t, float* w) {
-  const float z = 1.f - t;
-  w[1] = (t * t * (t - 2.f) * 3.f + 4.f) / 6.f;
-  w[2] = (z * z * (z - 2.f) * 3.f + 4.f) / 6.f;
-  w[0] = z * z * z / 6.f;
-  w[3] = 1.f - w[0] - w[1] - w[2];
-}
-
-// taps floor(x) - 1 .. floor(x) + 2 mirrored onto [0, n), and the weights of x's fraction
-__device__ __forceinline__ void cubic_taps(double x, int n, int* idx, float* w) {
-  const double f = floor(x);
-  cubic_weights((float)(x - f), w);
-  const int s = (int)f - 1;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) idx[k] = mirror_index(s + k, n);
-}
-
 __device__ __forceinline__ float cubic_eval(const float* __restrict__ c, int H, int W,
                                             const int* iz, const int* iy, const int* ix,
                                             const float* wz, const float* wy, const float* wx) {
@@ -178,17 +126,7 @@ __global__ __launch_bounds__(256) void affine_sample_kernel(
           lab[k] = seg[((int64_t)zi[a] * H + yi[b]) * W + xi[d]];
           w[k] = (uz[a] * uy[b]) * ux[d];
         }
-        bool found = false;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          double s = 0.0;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) s += lab[j] == lab[k] ? w[j] : 0.0;
-          if (s >= 0.5 && (!found || lab[k] > best)) {
-            best = lab[k];
-            found = true;
-          }
-        }
+        best = label_vote(lab, w);
       }
       oseg[idx] = best;
     }
@@ -377,21 +315,6 @@ __global__ __launch_bounds__(64) void stats_finish_kernel(const double* __restri
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
-static int aug_check_volume(const char* who, int64_t N, int64_t D, int64_t H, int64_t W) {
-  if (!(N >= 1 && D >= 1 && H >= 1 && W >= 1))
-    return fail(WF_E_SHAPE, std::string(who) + ": empty volume");
-  const int64_t lim = (int64_t)1 << 31;
-  if (!(D < lim && H < lim && W < lim && D * H < lim && D * H * W < lim))
-    return fail(WF_E_SHAPE, std::string(who) + ": D*H*W must be below 2^31 voxels");
-  if (!(N < lim && N * D * H * W < ((int64_t)1 << 40)))
-    return fail(WF_E_SHAPE, std::string(who) + ": N*D*H*W must be below 2^40");
-  return WF_OK;
-}
-
-static unsigned aug_grid(int64_t n) {
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(n, 256), 8192));
-}
-
 // the FIR along `axis` of N planes (D, H, W); n_out is the output's length along that axis
 static int launch_fir(const char* who, int mode, const float* in, float* out, int64_t N,
                       int64_t D, int64_t H, int64_t W, int axis, int64_t n_out,
@@ -440,11 +363,7 @@ extern "C" int wf_spline_prefilter_axis(const float* in, float* out, int64_t N, 
       return check_launch("wf_spline_prefilter_axis (copy)");
     return WF_OK;
   }
-  FirTaps t;
-  const double pole = sqrt(3.0) - 2.0;
-  double v = sqrt(3.0);  // gain 6 times -p / (1 - p^2)
-  t.r = AUG_SPLINE_TAPS;
-  for (int k = 0; k <= t.r; ++k, v *= pole) t.w[k] = (float)v;
+  const FirTaps t = spline_taps();
   const bool edge = mode == WF_SPLINE_EDGE;
   return launch_fir(__func__, edge ? FIR_EDGEPAD : FIR_MIRROR, in, out, N, D, H, W, axis,
                     edge ? n + 2 * AUG_PAD : n, t, s);

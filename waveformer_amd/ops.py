@@ -2311,3 +2311,85 @@ def channel_stats(x: torch.Tensor, guard: bool = False) -> torch.Tensor:
     if guard and not check_guard(ws, nbytes):
         raise RuntimeError("wf_channel_stats wrote past its workspace")
     return stats
+
+
+# ------------------------------------------------------------------------------------------
+# resampling (csrc/resample.hip)
+# ------------------------------------------------------------------------------------------
+ZOOM_AXIS_ORDER = (0, 1, 2)  # zoom_cubic_volume's passes: D, then H, then W
+
+
+def spline_zoom_axis(x: torch.Tensor, axis: int, on: int, clip: Optional[torch.Tensor] = None,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One axis (0 = D, 1 = H, 2 = W) of zoom(order=3, mode='nearest', grid_mode=True) on x
+    (N, D, H, W): edge-padded cubic prefilter and 4-tap interpolation in one launch
+    (wf_spline_zoom_axis).  clip: None, or the (N, 4) fp64 channel_stats rows whose [min, max]
+    the outputs of each plane are clamped to."""
+    shape = _planes4(x, "spline_zoom_axis")
+    on = int(on)
+    if axis not in (0, 1, 2) or on < 1:
+        raise ValueError(f"spline_zoom_axis: bad axis {axis!r} or length {on}")
+    if clip is not None:
+        _check(clip, "clip", dtype=torch.float64)
+        if tuple(clip.shape) != (shape[0], 4):
+            raise ValueError(f"spline_zoom_axis: clip {tuple(clip.shape)} != {(shape[0], 4)}")
+    oshape = list(shape)
+    oshape[1 + axis] = on
+    if out is None:
+        out = torch.empty(oshape, dtype=torch.float32, device=x.device)
+    else:
+        _check(out, "out")
+        if list(out.shape) != oshape:
+            raise ValueError(f"spline_zoom_axis: out {tuple(out.shape)} != {tuple(oshape)}")
+    _lib.call("wf_spline_zoom_axis", x.data_ptr(), out.data_ptr(), *shape, int(axis), on,
+              _ptr(clip), _stream())
+    return out
+
+
+def spline_zoom_axis_plan(n: int, on: int) -> list:
+    """The segments wf_spline_zoom_axis cuts an axis n -> on into, from the host-only
+    wf_spline_zoom_axis_plan: dicts with the outputs [o0, o1), the padded coefficients
+    [jlo, jhi], the input samples [slo, shi] and the two capacities.  Needs no GPU."""
+    nseg = _lib.query("wf_spline_zoom_axis_plan", int(n), int(on), 0, None)
+    if nseg < 0:
+        raise ValueError(f"spline_zoom_axis_plan: bad lengths {n} -> {on}")
+    keys = ("o0", "o1", "jlo", "jhi", "slo", "shi", "coef_cap", "samp_cap")
+    buf = (ctypes.c_int64 * 8)()
+    segs = []
+    for s in range(nseg):
+        if _lib.query("wf_spline_zoom_axis_plan", int(n), int(on), s, buf) != nseg:
+            raise RuntimeError("wf_spline_zoom_axis_plan: inconsistent segment count")
+        segs.append(dict(zip(keys, (int(v) for v in buf))))
+    return segs
+
+
+def zoom_cubic_volume(x: torch.Tensor, size: Sequence[int], clip: bool = True) -> torch.Tensor:
+    """skimage.transform.resize(order=3, mode='edge', anti_aliasing=False, clip=clip) of every
+    plane of x (N, D, H, W) to (N, *size): scipy's zoom(order=3, mode='nearest', grid_mode=True)
+    as one fused pass per axis in the order ZOOM_AXIS_ORDER (D, H, W), then, with clip, the
+    clamp to each plane's input [min, max] (channel_stats, applied by the last pass; nothing
+    crosses to the host).  An axis whose length does not change is skipped; when none changes x
+    itself is returned, as the reference returns its input."""
+    shape = _planes4(x, "zoom_cubic_volume")
+    size = _size3(size, "zoom_cubic_volume")
+    axes = [a for a in ZOOM_AXIS_ORDER if shape[1 + a] != size[a]]
+    if not axes:
+        return x
+    stats = channel_stats(x.view(shape[0], -1)) if clip else None
+    for a in axes:
+        x = spline_zoom_axis(x, a, size[a], clip=stats if a == axes[-1] else None)
+    return x
+
+
+def zoom_seg_linear(seg: torch.Tensor, size: Sequence[int]) -> torch.Tensor:
+    """batchgenerators' resize_segmentation(order=1) of seg (D, H, W) int16 to size
+    (wf_zoom_seg_linear): per output voxel the trilinear weights are summed per distinct label
+    and the largest label with a sum >= 0.5 wins, else 0."""
+    _check(seg, "seg", dtype=torch.int16)
+    if seg.dim() != 3:
+        raise ValueError(f"zoom_seg_linear: expected seg (D, H, W), got {tuple(seg.shape)}")
+    size = _size3(size, "zoom_seg_linear")
+    out = torch.empty(size, dtype=torch.int16, device=seg.device)
+    _lib.call("wf_zoom_seg_linear", seg.data_ptr(), *(int(v) for v in seg.shape), *size,
+              out.data_ptr(), _stream())
+    return out

@@ -24,9 +24,15 @@ base default_preprocessor.py DefaultPreprocessor.run_case_npy, :155-228) on HIP 
     voxel in C order".  Nothing of the size of the volume crosses to the host, and the samples
     equal the reference's.
 
-Not implemented: resampling.  The reference resamples with skimage.transform.resize when
-compute_new_shape differs from the cropped shape; run_case_npy raises NotImplementedError then
-(BraTS at 1 mm isotropic with out_spacing 1 mm never resamples).  File I/O (read_data, run,
+  * resampling (resampling/default_resampling.py, waveformer_amd.resampling): when
+    compute_new_shape differs from the cropped shape the reference resizes the normalised data
+    (order 3, clamped to each channel's range) and the segmentation (per label, order 1).
+    MultiModalityPreprocessor(resample=True) does the same on the device (csrc/resample.hip) and
+    draws class_locations on the resampled segmentation; with the default resample=False such a
+    case raises NotImplementedError, as before (BraTS at 1 mm isotropic with out_spacing 1 mm
+    never resamples).
+
+File I/O (read_data, run,
 run_plan: SimpleITK and the dataset plan) is out of scope, and `intensity_statistics_per_channel`
 is left out (the reference calls it unused at :428).  Segmentations hold integer labels that fit
 int16.  GPU only: host inputs are moved to the current device, and there is no CPU fallback.
@@ -39,6 +45,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .resampling import compute_new_shape, resample_data_or_seg_to_shape  # noqa: F401
 
 ArrayLike = Union[np.ndarray, torch.Tensor]
 NUM_SAMPLES = 10000          # default_preprocessor.py:415, :457
@@ -51,14 +58,6 @@ PROPERTY_KEYS = ("original_spacing_trans", "target_spacing_trans", "shape_before
 # ------------------------------------------------------------------------------------------
 # host arithmetic (no GPU needed)
 # ------------------------------------------------------------------------------------------
-def compute_new_shape(old_shape: Sequence[int], old_spacing: Sequence[float],
-                      new_spacing: Sequence[float]) -> np.ndarray:
-    """resampling/default_resampling.py:23-30, with Python's int(round(...)) (half to even)."""
-    if not (len(old_spacing) == len(old_shape) == len(new_spacing)):
-        raise ValueError("compute_new_shape: shape and spacings must have one length")
-    return np.array([int(round(i / j * k)) for i, j, k in zip(old_spacing, new_spacing, old_shape)])
-
-
 def target_num_samples(n: int, num_samples: int = NUM_SAMPLES,
                        min_percent_coverage: float = MIN_PERCENT_COVERAGE) -> int:
     """default_preprocessor.py:475-476: max(min(num_samples, n), ceil(n * coverage))."""
@@ -205,17 +204,20 @@ def collect_foreground_intensities(segmentation: ArrayLike, images: ArrayLike, s
 
 class MultiModalityPreprocessor:
     """preprocessor_mri.py:32 MultiModalityPreprocessor, the array part: same constructor
-    arguments, with out_spacing and all_labels (which the reference's run() sets) as keywords."""
+    arguments, with out_spacing and all_labels (which the reference's run() sets) as keywords,
+    and resample: whether a case whose spacing differs from out_spacing is resampled on the GPU
+    (waveformer_amd.resampling) or refused."""
 
     def __init__(self, base_dir=None, image_dir=None, data_filenames=(), seg_filename="", *,
                  out_spacing: Sequence[float] = (1.0, 1.0, 1.0),
-                 all_labels: Sequence[int] = (1, 2, 3)) -> None:
+                 all_labels: Sequence[int] = (1, 2, 3), resample: bool = False) -> None:
         self.base_dir = base_dir
         self.image_dir = image_dir
         self.data_filenames = data_filenames
         self.seg_filename = seg_filename
         self.out_spacing = list(out_spacing)
         self.all_labels = list(all_labels)
+        self.resample = bool(resample)  # False: a case that needs resampling is refused
         self.foreground_intensity_properties_per_channel: dict = {}
         self.last_fill_rounds: Optional[int] = None  # sweep rounds of the last case's hole fill
 
@@ -233,9 +235,11 @@ class MultiModalityPreprocessor:
         """default_preprocessor.py:155-228.  data (C, D, H, W), seg (1, D, H, W) or None,
         properties with "spacing" (as SimpleITK gives it, x first).  Returns (data (C, d, h, w)
         fp32, seg (1, d, h, w) int8 -- int16 if its maximum exceeds 127) on the GPU and fills
-        PROPERTY_KEYS in properties; class_locations holds host arrays.  Raises
-        NotImplementedError when the spacings ask for a resample (not implemented: the
-        reference's skimage resize), ValueError for an all-zero case."""
+        PROPERTY_KEYS in properties; class_locations holds host arrays.  When the spacings ask
+        for a resample: with resample=True the reference's order -- crop, normalise, resample
+        the data (order 3), resample the segmentation (order 1), class_locations on the
+        resampled segmentation, then the int8 / int16 cast; otherwise NotImplementedError.
+        ValueError for an all-zero case."""
         x = _images(data)
         size = tuple(int(v) for v in x.shape[1:])
         s = None if seg is None else _labels(seg, size)
@@ -249,14 +253,25 @@ class MultiModalityPreprocessor:
         cropped = tuple(b[1] - b[0] for b in bbox)
         properties["shape_after_cropping_before_resample"] = cropped
         new_shape = compute_new_shape(cropped, original_spacing_trans, self.out_spacing)
-        if tuple(int(v) for v in new_shape) != cropped:
+        resampled = tuple(int(v) for v in new_shape) != cropped
+        if resampled and not self.resample:
             raise NotImplementedError(
                 f"spacing {original_spacing_trans} -> {self.out_spacing} resamples {cropped} to "
-                f"{tuple(int(v) for v in new_shape)}: resampling is not implemented")
+                f"{tuple(int(v) for v in new_shape)}: resampling is off (resample=False)")
         out = ops.crop_normalize(x, bbox, ops.box_moments(x, bbox))
         properties["shape_after_resample"] = new_shape
         seg16, maxv = ops.crop_seg(s, filled, bbox, -1)
         seg_out = seg16[None]
+        if resampled:
+            # the reference passes the spacing as read (x first) here; with force_separate_z
+            # left at False neither spacing enters the decision
+            spacing = list(properties["spacing"])
+            out = resample_data_or_seg_to_shape(out, new_shape, spacing, self.out_spacing,
+                                                order=3, order_z=0)
+            seg_out = resample_data_or_seg_to_shape(seg_out, new_shape, spacing,
+                                                    self.out_spacing, is_seg=True, order=1,
+                                                    order_z=0)
+            maxv = seg_out.max()  # stays on the device until the one read below
         properties["class_locations"] = sample_foreground_locations(seg_out, self.all_labels)
         if int(maxv.cpu().item()) <= 127:
             seg_out = seg_out.to(torch.int8)
