@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define WF_ABI_VERSION 27
+#define WF_ABI_VERSION 28
 
 enum { WF_PREC_BF16 = 0, WF_PREC_BF16X3 = 1, WF_PREC_FP16 = 2 };
 
@@ -458,9 +458,10 @@ int wf_window_attention_fwd(const float* x, const float* ln_w, const float* ln_b
  * bitwise what nlev such calls write.  Widths without a multi-level GEMM instantiation run as
  * those nlev calls.  At C = 48 with 256 or more (window, head) pairs in the launch there is no
  * qkv GEMM launch: the core computes q / k / v itself from the rasters and the weight, bitwise
- * the GEMM's values (wf_window_attention_levels_fused tells), and the qkv part of the workspace
- * is not written.  wf_window_attention_fwd_table without norm1 takes the same rule.  workspace: wf_window_attention_levels_workspace_bytes(...) bytes (the sum
- * of the per-level sizes; < 0 for an invalid level list), 256-B aligned.                     */
+ * the GEMM's values (wf_window_attention_plan tells), and the qkv part of the workspace is not
+ * written.  wf_window_attention_fwd_table without norm1 takes the same rule.
+ * workspace: wf_window_attention_levels_workspace_bytes(...) bytes (the sum of the per-level
+ * sizes; < 0 for an invalid level list), 256-B aligned.                                      */
 int64_t wf_window_attention_levels_workspace_bytes(const int64_t* dhw, int nlev, int64_t B,
                                                    int64_t C, int precision);
 int wf_window_attention_fwd_levels(const float* const* x, const int64_t* dhw, int nlev,
@@ -479,10 +480,30 @@ int wf_window_attention_fwd_levels_mode(const float* const* x, const int64_t* dh
                                         const float* bproj, float* out, void* workspace,
                                         int64_t B, int64_t C, int64_t heads, float scale,
                                         int precision, void* stream, int qkv_mode);
-/* 1 if the rule computes q / k / v in the core for this level list, else 0 (also for an invalid
- * list).  Host only.                                                                          */
-int wf_window_attention_levels_fused(const int64_t* dhw, int nlev, int64_t B, int64_t C,
-                                     int64_t heads, int precision);
+/* Host only (no launch, no GPU needed): what a window attention call over these shapes launches,
+ * computed by the functions the forward entry points use (csrc/attn_plan.hpp), for 16-byte
+ * aligned sources.  dhw: nlev (D, H, W) triples.  flags: 1 the bias is the table (else dense) |
+ * 2 a LayerNorm in the qkv loader | 4 training, the core writes the log-sum-exp | 8 the call is
+ * one raster (wf_window_attention_fwd, _fwd_table, _fwd_train: nlev 1, any ws and head_dim);
+ * without 8 it is a level list (wf_window_attention_fwd_levels[_mode]: flags 1, ws 8).  qkv_mode
+ * as in wf_window_attention_fwd_levels_mode.  Returns 0, or a negative WF_E_* with wf_last_error
+ * set.  A launch set is: the qkv GEMM (or nothing), the core, the proj GEMM.  fields, 32 values:
+ *   [0] core: 1 table bias, 0 dense bias          [1] head_dim
+ *   [2] grouping: 0 merged, one launch set over all levels; else a launch set per level, because
+ *       1 no multi-level GEMM instantiation takes this width, 2 a level on the core's
+ *       one-sub-tile loop comes ahead of one on its query-pair loop, 3 the call is one raster
+ *   [3] the number of launch sets (1, or nlev: set i is level i)
+ *   [4] [5] [6] byte offsets in the workspace of qkv and of the core's output, and the total
+ *       (== wf_window_attention[_levels]_workspace_bytes); per-level sets use the same workspace
+ *       one after the other          [7] 0 (reserved)
+ *   [8 + 5 i ...] launch set i < 4 (0 past the last): q/k/v source, 0 staged (a qkv GEMM launch)
+ *       or 1 fused (computed in the core: no GEMM launch, qkv not written); wh, its (window,
+ *       head) pairs; qsplit, workgroups per pair (1 / 2 / 4; dense core: 0); pair_windows, its
+ *       first windows that may take the query-pair loop; the core launch's grid size
+ *   [28 + l] level l < 4: the tile loop it takes, NQ = 1 or 2 (dense core and past nlev: 0)   */
+int wf_window_attention_plan(const int64_t* dhw, int nlev, int64_t B, int64_t C, int64_t heads,
+                             int64_t ws, int precision, int flags, int qkv_mode,
+                             int64_t* fields);
 
 /* ---- a6: multi-scale fuse ------------------------------------------------------------- */
 /* Replaces the F.interpolate(trilinear, align_corners=False) + sum + shortcut of

@@ -20,6 +20,7 @@ argued here but counted by running_max_events and pinned in test_attention_softm
 """
 from __future__ import annotations
 
+import ctypes
 import functools
 import math
 import os
@@ -40,10 +41,6 @@ ROW_FLOOR = 64 * 2.0 ** -24   # ... and at least this
 LOG2E32 = np.float32(1.4426950408889634)
 MAX_BIAS = 96.0
 
-# ---- the launch rule of the table kernel, as csrc has it (read back by the host test) -------
-PAIR_LOOP_WH = 256    # attn_levels.hpp kAttnPairLoopWH: from here on qsplit <= 2
-NO_SPLIT_WH = 512     # attention.hip launch_attn_core: wh >= 512 -> qsplit 1
-PAIR_NSUB = 16        # attention.hip attn_tbl_kernel: nsub >= 16 -> the NQ = 2 loop
 TAU = {"bf16x3": 16.0, "bf16": 16.0, "fp16": 15.0}   # the lazy-rescale threshold per kind
 TBLN = 547
 WS, HD, HEADS, C = 8, 16, 3, 48
@@ -57,24 +54,42 @@ FORMS = {
 }
 
 
+PLAN_TABLE, PLAN_LN, PLAN_LSE, PLAN_RASTER = 1, 2, 4, 8   # wf_window_attention_plan's flags
+MERGED, NO_LEVELS_GEMM, PREFIX, ONE_RASTER = range(4)     # ... and its grouping field
+
+
+def window_attention_plan(levels, B, C, heads=None, ws=WS, prec=1, flags=PLAN_TABLE, qkv_mode=-1):
+    """What the library launches for a window attention call, asked without a launch
+    (wf_window_attention_plan; the field order is documented in include/waveformer_hip.h).
+    Raises RuntimeError with the library's message where the call would be refused."""
+    from waveformer_amd import _lib
+    flat = [v for l in levels for v in l]
+    f = (ctypes.c_int64 * 32)(*([-7] * 32))
+    _lib.call("wf_window_attention_plan", (ctypes.c_int64 * max(1, len(flat)))(*flat), len(levels),
+              B, C, C // 16 if heads is None else heads, ws, prec, flags, qkv_mode, f)
+    f = list(f)
+    n = f[3]
+    sets = [dict(zip(("fused", "wh", "qsplit", "pair_windows", "grid"), f[8 + 5 * i:13 + 5 * i]))
+            for i in range(n)]
+    assert f[7] == 0 and not any(f[8 + 5 * n:28]) and not any(f[28 + len(levels):])
+    return {"table": f[0], "head_dim": f[1], "grouping": f[2], "qkv": f[4], "ao": f[5],
+            "bytes": f[6], "sets": sets, "nq": f[28:28 + len(levels)]}
+
+
 def launch_form(wh: int) -> Tuple[int, int]:
-    """(qsplit, NQ) of a table-kernel launch over wh (window, head)s."""
-    qsplit = 1 if wh >= NO_SPLIT_WH else (2 if wh >= PAIR_LOOP_WH else 4)
-    return qsplit, (2 if N // 16 // qsplit >= PAIR_NSUB else 1)
+    """(qsplit, NQ) of a table-kernel launch over wh (window, head)s: wh one-head windows."""
+    p = window_attention_plan([(WS, WS, WS)], wh, HD, flags=PLAN_TABLE | PLAN_RASTER)
+    assert p["sets"][0]["wh"] == wh and p["sets"][0]["grid"] == wh * p["sets"][0]["qsplit"]
+    return p["sets"][0]["qsplit"], p["nq"][0]
 
 
 def launch_rule_in_source() -> Dict[str, float]:
-    """The three values of the launch rule and the thresholds, read from the kernel source."""
+    """The lazy-rescale thresholds (arithmetic of the kernel, not dispatch), read from its source."""
     csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "waveformer_amd", "csrc")
-    with open(os.path.join(csrc, "attn_levels.hpp")) as f:
-        hpp = f.read()
     with open(os.path.join(csrc, "attention.hip")) as f:
         hip = f.read()
     one = lambda pat, text: re.search(pat, text).group(1)  # noqa: E731
     return {
-        "pair_loop_wh": int(one(r"constexpr int64_t kAttnPairLoopWH = (\d+);", hpp)),
-        "no_split_wh": int(one(r"const int qsplit = wh >= (\d+) \? 1 : \(attn_tbl_pair_loop\(wh\) \? 2 : 4\);", hip)),
-        "pair_nsub": int(one(r"if \(nsub >= (\d+) && bw < pair_end\)", hip)),
         "tau": float(one(r"constexpr float kTau = ([0-9.]+)f;", hip)),
         "tau_fp16": float(one(r"constexpr float kTauFp16 = ([0-9.]+)f;", hip)),
     }

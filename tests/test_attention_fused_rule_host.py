@@ -1,12 +1,13 @@
 """CPU: the rule that lets the table-bias attention core compute q / k / v itself instead of
-reading a staged qkv tensor (wf_window_attention_levels_fused, attn_levels.hpp attn_qkv_fused):
-C = 48 and at least 256 (window, head) pairs in the launch.  C = 96 has a fused instantiation
-(qkv_mode 1) but the rule leaves it staged: its B = 8 launch measured slower fused than the GEMM
-and the core together.  Host only, no GPU."""
+reading a staged qkv tensor (the q/k/v-source field of wf_window_attention_plan, attn_plan.hpp
+attn_qkv_fused): C = 48 and at least 256 (window, head) pairs in the launch.  C = 96 has a fused
+instantiation (qkv_mode 1) but the rule leaves it staged: its B = 8 launch measured slower fused
+than the GEMM and the core together.  Host only, no GPU."""
 import ctypes
 
 import pytest
 
+from tests.attention_cases import window_attention_plan
 from waveformer_amd import _lib
 
 FAKE = 256  # never dereferenced: validation fails first
@@ -21,15 +22,17 @@ def _dhw(levels):
 
 
 def _fused(B, C, levels, prec=1):
-    return _lib.query("wf_window_attention_levels_fused", _dhw(levels), len(levels), B, C, C // 16,
-                      prec)
+    """The one q/k/v source of the call's launch sets: 1 computed in the core, 0 staged."""
+    (src,) = {s["fused"] for s in window_attention_plan(levels, B, C, prec=prec)["sets"]}
+    return src
 
 
 def test_symbols_exported():
     lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in ("wf_window_attention_fwd_levels_mode", "wf_window_attention_levels_fused"):
+    for name in ("wf_window_attention_fwd_levels_mode", "wf_window_attention_plan"):
         assert hasattr(lib, name), name
         assert name in _lib.SIGNATURES
+    assert not hasattr(lib, "wf_window_attention_levels_fused")
 
 
 @pytest.mark.parametrize("prec", [0, 1, 2])
@@ -46,8 +49,10 @@ def test_rule_threshold_and_bad_lists():
     # 86 windows x 3 = 258 >= 256 > 85 x 3
     assert _fused(86, 48, [(8, 8, 8)]) == 1
     assert _fused(85, 48, [(8, 8, 8)]) == 0
-    assert _fused(8, 48, [(12, 12, 12)]) == 0
-    assert _fused(8, 48, L3, prec=7) == 0
+    with pytest.raises(RuntimeError, match="8\\^3 windows"):
+        _fused(8, 48, [(12, 12, 12)])
+    with pytest.raises(RuntimeError, match="unknown precision"):
+        _fused(8, 48, L3, prec=7)
 
 
 def test_mode_is_validated_on_the_host():
@@ -64,3 +69,6 @@ def test_mode_is_validated_on_the_host():
     assert rc < 0 and "C = 48 and 96" in msg
     rc, msg = fwd(48, 2)
     assert rc < 0 and "qkv_mode" in msg
+    for C, mode, text in ((192, 1, "C = 48 and 96"), (48, 2, "qkv_mode")):   # the query agrees
+        with pytest.raises(RuntimeError, match=text):
+            window_attention_plan([(8, 8, 8)], 8, C, qkv_mode=mode)

@@ -2,8 +2,10 @@
 
  * The operand-rounding emulation with no rounding IS the fp64 reference (1e-12), on a q.k-driven
    input and on a bias-only one (the shared-probability shortcut against the per-window path).
- * The launch rule the cases are built for is the one in the kernel source: kAttnPairLoopWH,
-   the wh >= 512 split, nsub >= 16 for the query-pair loop, and the lazy-rescale thresholds.
+ * The launch rule the cases are built for is the one the library follows, asked of it without a
+   launch (wf_window_attention_plan): the split over 4 / 2 / 1 workgroups with its boundaries at
+   256 and 512 (window, head)s and the tile loop each takes; and the lazy-rescale thresholds are
+   the ones in the kernel source.
  * Every bias-only table case reaches, in every launch form it runs in, each event it claims
    (running_max_events, an fp32 emulation of attn_tbl_tiles' running-max rule alone):
      a  a tile after the first rescales            b  a kept tile with s - mrun > 8
@@ -23,9 +25,9 @@ from tests import attention_cases as A
 
 def test_launch_rule_matches_the_source():
     src = A.launch_rule_in_source()
-    assert src == {"pair_loop_wh": A.PAIR_LOOP_WH, "no_split_wh": A.NO_SPLIT_WH,
-                   "pair_nsub": A.PAIR_NSUB, "tau": A.TAU["bf16x3"], "tau_fp16": A.TAU["fp16"]}
+    assert src == {"tau": A.TAU["bf16x3"], "tau_fp16": A.TAU["fp16"]}
     assert A.TAU["bf16"] == A.TAU["bf16x3"]
+    assert len(A.FORMS) == 3
     for form, (windows, raster, qsplit, nq) in A.FORMS.items():
         assert windows * A.N == raster[0] * raster[1] * raster[2]
         assert A.launch_form(windows * A.HEADS) == (qsplit, nq), form

@@ -85,6 +85,50 @@ def test_levels_from_band_buffer_views(prec):
         assert torch.equal(m, s)
 
 
+# case -> B, C, levels, and what wf_window_attention_plan must say: the grouping and each launch
+# set's q/k/v source.  The smallest shapes that reach each grouping and source: C = 48 merges
+# (gemm_rows<9>), C = 192 has no multi-level GEMM, 11 x 8 windows x 3 heads = 264 pairs are fused.
+PLAN_CASES = {
+    "merged_staged": (1, 48, [(16, 16, 16), (8, 8, 8)], "MERGED", [0]),
+    "per_level": (1, 192, [(16, 16, 16), (8, 8, 8)], "NO_LEVELS_GEMM", [0, 0]),
+    "fused": (11, 48, [(16, 16, 16)], "MERGED", [1]),
+}
+
+
+@pytest.mark.parametrize("case", sorted(PLAN_CASES))
+def test_workspace_use_is_what_the_plan_says(case):
+    """The workspace claims of the plan: a call stays within the plan's `bytes` (per-level launch
+    sets re-use the one workspace), and a fused launch set does not write the qkv area.  The
+    workspace has ops.GUARD_BYTES of guard behind it and its qkv area is pre-filled."""
+    _gpu()
+    import ctypes
+    from tests import attention_cases as A
+    from waveformer_amd import _lib, ops
+    B, C, levels, grouping, fused = PLAN_CASES[case]
+    heads, prec, scale = C // 16, ops.PRECISIONS["bf16x3"], 16 ** -0.5
+    plan = A.window_attention_plan(levels, B, C, prec=prec)
+    assert plan["grouping"] == getattr(A, grouping)
+    assert [s["fused"] for s in plan["sets"]] == fused
+    w = _weights(C, heads, 400)
+    xs = [seeded_randn((B, *dhw, C), 50 + i).cuda() for i, dhw in enumerate(levels)]
+    work = ops._workspace(plan["bytes"], "cuda", case, guard=True)
+    work[:plan["ao"]] = 0x5A
+    out = torch.empty((sum(x.numel() // C for x in xs), C), device="cuda")
+    wq, wp = ops.split_weight(w["wqkv"], prec=prec), ops.split_weight(w["wproj"], prec=prec)
+    _lib.call("wf_window_attention_fwd_levels_mode",
+              (ctypes.c_void_p * len(xs))(*[x.data_ptr() for x in xs]),
+              (ctypes.c_int64 * (3 * len(xs)))(*[v for dhw in levels for v in dhw]), len(xs),
+              wq.data_ptr(), w["bqkv"].data_ptr(), w["table"].data_ptr(), wp.data_ptr(),
+              w["bproj"].data_ptr(), out.data_ptr(), work.data_ptr(), B, C, heads, scale, prec,
+              ops._stream(), -1)
+    assert ops.check_guard(work, plan["bytes"])
+    if fused == [1]:
+        assert bool((work[:plan["ao"]] == 0x5A).all())
+    a = (w["wqkv"], w["bqkv"], w["table"], w["wproj"], w["bproj"], 8, heads, scale)
+    single = [ops.window_attention(x, *a, prec=prec).reshape(-1, C) for x in xs]
+    assert torch.isfinite(out).all() and torch.equal(out, torch.cat(single))
+
+
 def test_levels_op_schema_and_fake():
     """waveformer::window_attn_levels: schema and fake-tensor checks (inference only: the op
     registers no autograd), and its one buffer holds the levels' outputs in order."""

@@ -98,7 +98,7 @@ SIGNATURES = {
                                             _I64, _F, _I, _P]),
     "wf_window_attention_fwd_levels_mode": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I64,
                                                  _I64, _I64, _F, _I, _P, _I]),
-    "wf_window_attention_levels_fused": (_I, [_P, _I, _I64, _I64, _I64, _I]),
+    "wf_window_attention_plan": (_I, [_P, _I, _I64, _I64, _I64, _I64, _I, _I, _I, _P]),
     "wf_msfuse_fwd": (_I, [_P, _P, _I, _P, _P, _P, _P, _F, _I64, _I64, _I64, _I64, _I64, _P]),
     "wf_ccf_ffn_workspace_bytes": (_I64, [_I64, _I64, _I64, _I64, _I64, _I64, _I]),
     "wf_ccf_ffn_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _F, _P, _P,
@@ -179,7 +179,7 @@ SIGNATURES = {
     "wf_zoom_seg_linear": (_I, [_P] + [_I64] * 6 + [_P, _P]),
 }
 
-ABI_VERSION = 27
+ABI_VERSION = 28
 _lock = threading.Lock()
 _lib = None
 _err = None

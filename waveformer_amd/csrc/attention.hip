@@ -16,12 +16,12 @@
 //          carries Q, K, V and P as bf16 hi + lo pairs (3 MFMAs per product).
 //   proj : gemm_ares; rows stay in window-major order, which is exactly the reference's
 //          reshaped raster (Q1).
-#include "attn_levels.hpp"
+//   host : what a call launches is decided in attn_plan.hpp (AttnPlan) and run
+//          by run_window_attention below.
+#include "attn_plan.hpp"
 #include "gemm_common.hpp"
 
 namespace wf {
-
-constexpr int kQB = 64;  // queries per workgroup (16 per wave)
 
 // XCD-contiguous decode of the 1-D grid: the query tiles of one (window, head), which all stage
 // the same K / V rows, run on one XCD instead of fetching those rows into 8 L2s
@@ -729,7 +729,7 @@ __global__ __launch_bounds__(512, 2) void attn_tbl_kernel(const void* __restrict
 
   const int nsub = N / 16 / qsplit;  // 16-query sub-tiles of this workgroup
   const int q0 = qs * (N / qsplit);
-  if (nsub >= 16 && bw < pair_end)
+  if (nsub >= kAttnPairNsub && bw < pair_end)
     attn_tbl_tiles<P, 2>(qkv, nullptr, out, tq, Ks, Vq, row0, q0, h, heads, nsub, scale_log2);
   else
     attn_tbl_tiles<P, 1>(qkv, nullptr, out, tq, Ks, Vq, row0, q0, h, heads, nsub, scale_log2);
@@ -762,54 +762,47 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 
   const int nsub = N / 16 / qsplit;  // 16-query sub-tiles of this workgroup
   const int q0 = qs * (N / qsplit);
-  if (nsub >= 16 && bw < pair_end)
+  if (nsub >= kAttnPairNsub && bw < pair_end)
     attn_tbl_tiles<P, 2, CW>(nullptr, &g, out, tq, Ks, Vq, row0, q0, h, heads, nsub, scale_log2);
   else
     attn_tbl_tiles<P, 1, CW>(nullptr, &g, out, tq, Ks, Vq, row0, q0, h, heads, nsub, scale_log2);
 }
 
-bool attn_tbl_pair_loop(int64_t wh) { return wh >= kAttnPairLoopWH; }
-
-int launch_attn_core(const void* qkv, const float* bias, void* out, float* lse, int64_t Bw,
-                     int N, int heads, int hd, float scale, int prec, hipStream_t s,
-                     int table_ws, int64_t pair_windows, const GemmArgs* fused) {
-  if (Bw <= 0) return WF_OK;
-  const int64_t nblk = cdiv(N, kQB) * heads * Bw;
-  if (nblk > 0x7fffffff) return fail(WF_E_SHAPE, "attention: too many (window, head) tiles");
-  dim3 grid((unsigned)nblk);  // 1-D, decoded XCD-aware by attn_block
+// The core launch of launch set t of p over a (rows, 3C) qkv buffer (bf16, or fp32 when the
+// precision stores fp32).  fused: the qkv GEMM's argument block (MAP_LEVELS rows); the table
+// core then computes q / k / v itself from x and the weight and `qkv` is not read.
+static int launch_attn_core(const AttnPlan& p, const AttnSet& t, const void* qkv, const float* bias,
+                            void* out, float* lse, float scale, hipStream_t s,
+                            const GemmArgs* fused) {
+  if (t.grid <= 0) return WF_OK;
+  const dim3 grid((unsigned)t.grid);  // 1-D, decoded XCD-aware by attn_block
   const float sl2 = scale * 1.4426950408889634f;
-  const bool split = prec == PREC_SPLIT;
-  const bool f16 = prec == PREC_FP16;
-  if (!valid_prec(prec)) return fail(WF_E_SHAPE, "attention: unknown precision");
-  if (table_ws) {  // bias = the (T, heads) table; index from the coordinates
-    if (table_ws != 8 || hd != 16 || N != 512)
-      return fail(WF_E_SHAPE, "attention (table bias): implemented for ws = 8, head_dim = 16");
-    if (lse) return fail(WF_E_SHAPE, "attention (table bias): inference only, no log-sum-exp");
-    // queries of one (window, head) split over 1, 2 or 4 workgroups: enough workgroups for
-    // two per CU, each staging the window's K / V once
-    const int64_t wh = Bw * heads;
-    const int qsplit = wh >= 512 ? 1 : (attn_tbl_pair_loop(wh) ? 2 : 4);
-    const dim3 g1((unsigned)(wh * qsplit));
+  const bool split = p.prec == PREC_SPLIT;
+  const bool f16 = p.prec == PREC_FP16;
+  const int heads = (int)p.heads;
+  if (p.table) {  // bias = the (T, heads) table; index from the coordinates
     auto k = split ? attn_tbl_kernel<PREC_SPLIT>
                    : (f16 ? attn_tbl_kernel<PREC_FP16> : attn_tbl_kernel<PREC_BF16>);
-    const int64_t pair_end = pair_windows < 0 ? Bw : pair_windows;
-    if (fused) {  // q / k / v from x and the weight: *fused is the qkv GEMM's argument block
+    if (fused) {  // q / k / v from x and the weight
       void (*kf)(GemmArgs, const float*, void*, int, int, float, int64_t) = nullptr;
 #define ATTN_FUSED_CASE(CWV)                                                               \
   if (fused->K == CWV)                                                                     \
     kf = split ? attn_tbl_kernel_fused<PREC_SPLIT, CWV>                                    \
                : (f16 ? attn_tbl_kernel_fused<PREC_FP16, CWV> : attn_tbl_kernel_fused<PREC_BF16, CWV>);
-      ATTN_FUSED_CASE(48)
-      ATTN_FUSED_CASE(96)
+      ATTN_FUSED_CASE(kAttnFusedWidths[0])
+      ATTN_FUSED_CASE(kAttnFusedWidths[1])
 #undef ATTN_FUSED_CASE
       if (!kf || !gemm_levels_callsite(*fused) || fused->N != 3 * fused->K || heads * 16 != fused->K)
         return fail(WF_E_SHAPE, "attention core (q/k/v in the core): instantiated for C = 48 and 96");
-      hipLaunchKernelGGL(kf, g1, dim3(512), 0, s, *fused, bias, out, heads, qsplit, sl2, pair_end);
+      hipLaunchKernelGGL(kf, grid, dim3(512), 0, s, *fused, bias, out, heads, t.qsplit, sl2,
+                         t.pair_windows);
       return check_launch("attention core (table bias, q/k/v in the core)");
     }
-    hipLaunchKernelGGL(k, g1, dim3(512), 0, s, qkv, bias, out, heads, qsplit, sl2, pair_end);
+    hipLaunchKernelGGL(k, grid, dim3(512), 0, s, qkv, bias, out, heads, t.qsplit, sl2,
+                       t.pair_windows);
     return check_launch("attention core (table bias, window per workgroup)");
   }
+  const int N = (int)(p.ws * p.ws * p.ws);
 #define ATTN_HD_CASE(HDV)                                                                  \
   case HDV: {                                                                              \
     auto k = split ? attn_core_kernel<HDV, (HDV >= 192 ? 32 : 64), PREC_SPLIT>             \
@@ -818,7 +811,7 @@ int launch_attn_core(const void* qkv, const float* bias, void* out, float* lse, 
     hipLaunchKernelGGL(k, grid, dim3(256), 0, s, qkv, bias, out, lse, N, heads, sl2);      \
     break;                                                                                 \
   }
-  switch (hd) {
+  switch (p.head_dim) {
     ATTN_HD_CASE(16)
     ATTN_HD_CASE(32)
     ATTN_HD_CASE(48)
@@ -840,17 +833,6 @@ __global__ void rel_pos_bias_kernel(const float* __restrict__ table, const int64
   if (i >= NN) return;
   const int64_t r = index[i];
   for (int h = 0; h < heads; ++h) bias[h * NN + i] = table[r * heads + h];
-}
-
-// The workspace of a forward over `rows` tokens: qkv (rows, 3 C) at offset 0, the core's output
-// (rows, C) at `ao`, both in the precision's activation storage and 256-B aligned.
-struct AttnWorkspace {
-  int64_t ao, bytes;
-};
-static AttnWorkspace attn_workspace(int64_t rows, int64_t C, int prec) {
-  const int64_t e = store32(prec) ? 4 : 2;
-  const int64_t ao = align256(rows * 3 * C * e);
-  return {ao, ao + align256(rows * C * e)};
 }
 
 // qkv = Linear(window_partition(norm1?(x))) of a (B, D1, H1, W1, C) raster into (rows, 3 C)
@@ -886,29 +868,20 @@ static GemmArgs qkv_gemm_args(const float* x, const float* ln_w, const float* ln
   return g;
 }
 
-// the rows of g come from the levels of L (MAP_LEVELS)
-static void set_level_sources(GemmArgs& g, const float* const* x, const AttnLevels& L) {
+// the rows of g come from the n levels of L from level l0 on (MAP_LEVELS), x[0] being level l0's
+static void set_level_sources(GemmArgs& g, const float* const* x, const AttnLevels& L, int l0,
+                              int n) {
   g.a_map = MAP_LEVELS;
+  g.mD = g.mH = g.mW = 0;
+  g.a_eps = 0.f;
   for (int l = 0; l < WF_MAX_LEVELS; ++l) {
-    const bool on = l < L.nlev;
+    const bool on = l < n;
     g.lv_src[l] = on ? x[l] : x[0];
-    g.lv_row0[l] = on ? (int)L.row0[l] : 0x7fffffff;
-    g.lv_D[l] = on ? L.D[l] : kAttnLevelsWs;
-    g.lv_H[l] = on ? L.H[l] : kAttnLevelsWs;
-    g.lv_W[l] = on ? L.W[l] : kAttnLevelsWs;
+    g.lv_row0[l] = on ? (int)(L.row0[l0 + l] - L.row0[l0]) : 0x7fffffff;
+    g.lv_D[l] = on ? L.D[l0 + l] : kAttnLevelsWs;
+    g.lv_H[l] = on ? L.H[l0 + l] : kAttnLevelsWs;
+    g.lv_W[l] = on ? L.W[l0 + l] : kAttnLevelsWs;
   }
-}
-
-// whether a table-bias launch over `windows` windows computes q / k / v in the core; 0 / 1, or
-// < 0 with the error set when the fused form is asked for at a width it is not instantiated for
-static int pick_qkv_fused(int qkv_mode, int64_t windows, int64_t heads, int64_t C) {
-  if (qkv_mode == ATTN_QKV_STAGED) return 0;
-  if (qkv_mode == ATTN_QKV_FUSED) {
-    if (!attn_qkv_fused_width(C))
-      return fail(WF_E_SHAPE, "window attention: q/k/v in the core is instantiated for C = 48 and 96");
-    return 1;
-  }
-  return attn_qkv_fused(windows, heads, C) ? 1 : 0;
 }
 
 // out = Linear(core output); window-major rows == the reshaped raster (Q1)
@@ -934,6 +907,102 @@ static GemmArgs proj_gemm_args(const void* ao, const uint16_t* wproj, const floa
   return p;
 }
 
+// The plan of a call, or what is wrong with it: attn_plan, then the one input the plain header
+// cannot compute -- whether a streaming GEMM takes the merged qkv GEMM (only its shape is read)
+static const char* attn_plan_call(const int64_t* dhw, int nlev, int64_t B, int64_t C, int64_t heads,
+                                  int64_t ws, int prec, int flags, int qkv_mode, AttnPlan& p) {
+  if (!valid_prec(prec)) return "unknown precision";
+  auto levels_gemm = [&](int64_t rows) {
+    GemmArgs g = qkv_gemm_args(nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, rows, B,
+                               C, 0, 0, 0, ws, prec);
+    g.a_map = MAP_LEVELS;
+    GemmRowsPick r;
+    return gemm_rows_pick(g, true, r) || gemm_kc_pick_nt(g) > 0;
+  };
+  return attn_plan(dhw, nlev, B, C, heads, ws, prec, flags, qkv_mode, levels_gemm, p);
+}
+
+// the pointers of a call; x: one source per level
+struct AttnPtrs {
+  const float* const* x;
+  const float *ln_w, *ln_b;
+  float ln_eps;
+  const uint16_t* wqkv_bf16x2;
+  const float *bqkv, *bias;
+  const uint16_t* wproj_bf16x2;
+  const float* bproj;
+  float* out;
+  void* workspace;
+  float* lse;
+  float scale;
+};
+
+// The launch sets of p, one after the other: qkv GEMM (or nothing: q / k / v in the core), core,
+// proj GEMM.  The levels share the weights, the window and head_dim and do not depend on one
+// another, so a merged set is one problem of sum(rows) logical rows: the qkv GEMM gathers each
+// row from its level (MAP_LEVELS), the core runs over sum(windows), the proj GEMM is the
+// identity-map one.  Every row's arithmetic is what its level's own set does, so the two
+// groupings are bitwise equal: a GEMM row does not depend on the rows it shares a launch with,
+// and the core's result depends on its grid only through which of its two loops a window takes,
+// which the merged launch keeps per level (pair_windows).  A fused set computes q / k / v from
+// the rasters and the weight, bitwise the GEMM's values, and leaves the qkv area untouched.
+static int run_window_attention(const AttnPlan& p, const AttnPtrs& a, hipStream_t s) {
+  const AttnLevels& L = p.L;
+  const bool merged = p.grouping == ATTN_MERGED;
+  for (int l = 0; l < p.nsets; ++l) {  // the set's first level
+    const AttnSet& t = p.set[l];
+    void* qkv = a.workspace;
+    void* ao = reinterpret_cast<char*>(a.workspace) + t.ao;
+    // 1. qkv = Linear(window_partition(norm1?(x))): a launch, or the argument block the core
+    //    computes q / k / v from
+    GemmArgs g = qkv_gemm_args(a.x[l], a.ln_w, a.ln_b, a.ln_eps, a.wqkv_bf16x2, a.bqkv, qkv, t.rows,
+                               p.B, p.C, L.D[l], L.H[l], L.W[l], p.ws, p.prec);
+    if (merged || t.fused) set_level_sources(g, a.x + l, L, l, merged ? L.nlev : 1);
+    int rc = WF_OK;
+    if (!t.fused && merged) {  // the plan asked the two launchers' predicates
+      if (!try_launch_gemm_rows(g, s, true) && !try_launch_gemm_kc(g, s))
+        return fail(WF_E_LAUNCH, "window attention: no GEMM took the planned multi-level qkv");
+      rc = check_launch("wf_window_attention_fwd(qkv)");
+    } else if (!t.fused) {
+      rc = launch_gemm(g, s, "wf_window_attention_fwd(qkv)");
+    }
+    if (rc) return rc;
+    // 2. softmax(q k^T * scale + bias) v
+    rc = launch_attn_core(p, t, qkv, a.bias, ao, a.lse, a.scale, s, t.fused ? &g : nullptr);
+    if (rc) return rc;
+    // 3. proj; window-major rows == the reshaped raster (Q1), level after level
+    rc = launch_gemm(proj_gemm_args(ao, a.wproj_bf16x2, a.bproj, a.out + L.row0[l] * p.C, t.rows,
+                                    p.C, p.prec),
+                     s, "wf_window_attention_fwd(proj)");
+    if (rc) return rc;
+  }
+  return WF_OK;
+}
+
+// every forward entry point: validate the pointers, build the plan, run it
+static int window_attention_call(const char* who, const int64_t* dhw, int nlev, int64_t B,
+                                 int64_t C, int64_t heads, int64_t ws, int prec, int flags,
+                                 int qkv_mode, const AttnPtrs& a, void* stream) {
+#define ATTN_REQUIRE_PTR(ptr, name) \
+  if ((ptr) == nullptr) return fail(WF_E_NULLPTR, std::string(who) + ": " name " is NULL")
+  ATTN_REQUIRE_PTR(a.x, "x");
+  flags |= ATTN_ALIGNED;
+  for (int l = 0; l < nlev && l < kAttnMaxLevels; ++l)
+    if (reinterpret_cast<uintptr_t>(a.x[l]) % 16 != 0) flags &= ~ATTN_ALIGNED;
+  AttnPlan p;
+  if (const char* why = attn_plan_call(dhw, nlev, B, C, heads, ws, prec, flags, qkv_mode, p))
+    return fail(WF_E_SHAPE, std::string(who) + ": " + why);
+  for (int l = 0; l < nlev; ++l) ATTN_REQUIRE_PTR(a.x[l], "x");
+  ATTN_REQUIRE_PTR(a.wqkv_bf16x2, "wqkv_bf16x2");
+  ATTN_REQUIRE_PTR(a.bias, "bias");
+  ATTN_REQUIRE_PTR(a.wproj_bf16x2, "wproj_bf16x2");
+  ATTN_REQUIRE_PTR(a.out, "out");
+  ATTN_REQUIRE_PTR(a.workspace, "workspace");
+  if (a.ln_w) ATTN_REQUIRE_PTR(a.ln_b, "ln_b");
+#undef ATTN_REQUIRE_PTR
+  return run_window_attention(p, a, (hipStream_t)stream);
+}
+
 }  // namespace wf
 
 using namespace wf;
@@ -955,68 +1024,33 @@ extern "C" int64_t wf_window_attention_workspace_bytes(int64_t B, int64_t C, int
   return attn_workspace(B * D1 * H1 * W1, C, precision).bytes;
 }
 
-static int window_attention_impl(const float* x, const float* ln_w, const float* ln_b,
-                                 float ln_eps, const uint16_t* wqkv_bf16x2, const float* bqkv,
-                                 const float* bias, int table_ws,
-                                 const uint16_t* wproj_bf16x2, const float* bproj, float* out,
-                                 void* workspace, float* lse, int64_t B, int64_t C, int64_t D1,
-                                 int64_t H1, int64_t W1, int64_t ws, int64_t heads, float scale,
-                                 int precision, void* stream,
-                                 int qkv_mode = ATTN_QKV_STAGED) {
-  WF_REQUIRE(B >= 1 && C >= 8 && C % 8 == 0, "C must be a positive multiple of 8");
-  WF_REQUIRE(ws >= 1 && D1 % ws == 0 && H1 % ws == 0 && W1 % ws == 0,
-             "the raster must tile into ws^3 windows (window_partition, wave_helper.py:459)");
-  WF_REQUIRE(heads >= 1 && C % heads == 0, "dim must be divisible by num_heads");
-  WF_REQUIRE(valid_prec(precision), "unknown precision");
-  WF_REQUIRE_PTR(x);
-  WF_REQUIRE_PTR(wqkv_bf16x2);
-  WF_REQUIRE_PTR(bias);
-  WF_REQUIRE_PTR(wproj_bf16x2);
-  WF_REQUIRE_PTR(out);
-  WF_REQUIRE_PTR(workspace);
-  if (ln_w) WF_REQUIRE_PTR(ln_b);
-  const int64_t N = ws * ws * ws;
-  const int64_t rows = B * D1 * H1 * W1;
-  const int64_t Bw = rows / N;
-  hipStream_t s = (hipStream_t)stream;
-  void* qkv = workspace;
-  void* ao = reinterpret_cast<char*>(workspace) + attn_workspace(rows, C, precision).ao;
-  // the table-bias core without a LayerNorm in the loader may compute q / k / v itself: the
-  // raster as the one level of a MAP_LEVELS argument block (same rows as MAP_WINDOW's)
-  if (table_ws == kAttnLevelsWs && !ln_w && !lse && C == 16 * heads && rows <= 0x7fffffff &&
-      reinterpret_cast<uintptr_t>(x) % 16 == 0) {
-    const int fused = pick_qkv_fused(qkv_mode, Bw, heads, C);
-    if (fused < 0) return WF_E_SHAPE;
-    if (fused) {
-      const int64_t dhw[3] = {D1, H1, W1};
-      AttnLevels L;
-      if (const char* why = attn_levels_plan(dhw, 1, B, C, heads, L))
-        return fail(WF_E_SHAPE, std::string("window attention: ") + why);
-      GemmArgs g = qkv_gemm_args(x, nullptr, nullptr, 0.f, wqkv_bf16x2, bqkv, qkv, rows, B, C, 0, 0,
-                                 0, ws, precision);
-      set_level_sources(g, &x, L);
-      const int rc = launch_attn_core(nullptr, bias, ao, nullptr, Bw, (int)N, (int)heads, 16, scale,
-                                      precision, s, table_ws, -1, &g);
-      if (rc) return rc;
-      return launch_gemm(proj_gemm_args(ao, wproj_bf16x2, bproj, out, rows, C, precision), s,
-                         "wf_window_attention_fwd(proj)");
-    }
-  } else if (qkv_mode == ATTN_QKV_FUSED) {
-    return fail(WF_E_SHAPE, "window attention: q/k/v in the core needs the table bias (ws 8, "
-                            "head_dim 16), inference, no LayerNorm in the loader");
-  }
-  // 1. qkv = Linear(window_partition(norm1?(x)))
-  int rc = launch_gemm(qkv_gemm_args(x, ln_w, ln_b, ln_eps, wqkv_bf16x2, bqkv, qkv, rows, B, C,
-                                     D1, H1, W1, ws, precision),
-                       s, "wf_window_attention_fwd(qkv)");
-  if (rc) return rc;
-  // 2. softmax(q k^T * scale + bias) v
-  rc = launch_attn_core(qkv, bias, ao, lse, Bw, (int)N, (int)heads, (int)(C / heads), scale,
-                        precision, s, table_ws);
-  if (rc) return rc;
-  // 3. proj; window-major rows == the reshaped raster (Q1)
-  return launch_gemm(proj_gemm_args(ao, wproj_bf16x2, bproj, out, rows, C, precision), s,
-                     "wf_window_attention_fwd(proj)");
+extern "C" int64_t wf_window_attention_levels_workspace_bytes(const int64_t* dhw, int nlev,
+                                                              int64_t B, int64_t C,
+                                                              int precision) {
+  AttnLevels L;
+  if (attn_levels_plan(dhw, nlev, B, C, C / 16, L)) return WF_E_SHAPE;
+  return attn_workspace(L.row0[nlev], C, precision).bytes;
+}
+
+extern "C" int wf_window_attention_plan(const int64_t* dhw, int nlev, int64_t B, int64_t C,
+                                        int64_t heads, int64_t ws, int precision, int flags,
+                                        int qkv_mode, int64_t* fields) {
+  WF_REQUIRE(flags >= 0 && flags < ATTN_ALIGNED, "flags: 1 table bias | 2 LayerNorm | 4 lse | 8 one raster");
+  WF_REQUIRE_PTR(fields);
+  AttnPlan p{};  // the sets and levels a plan does not use read as 0
+  if (const char* why = attn_plan_call(dhw, nlev, B, C, heads, ws, precision, flags | ATTN_ALIGNED,
+                                       qkv_mode, p))
+    return fail(WF_E_SHAPE, std::string(__func__) + ": " + why);
+  int64_t* f = fields;
+  for (int64_t v : {(int64_t)p.table, (int64_t)p.head_dim, (int64_t)p.grouping, (int64_t)p.nsets,
+                    p.work.qkv, p.work.ao, p.work.bytes, (int64_t)0})
+    *f++ = v;
+  for (int i = 0; i < kAttnMaxLevels; ++i)
+    for (int64_t v : {(int64_t)p.set[i].fused, p.set[i].wh, (int64_t)p.set[i].qsplit,
+                      p.set[i].pair_windows, p.set[i].grid})
+      *f++ = i < p.nsets ? v : 0;
+  for (int l = 0; l < kAttnMaxLevels; ++l) *f++ = l < p.L.nlev ? p.nq[l] : 0;
+  return WF_OK;
 }
 
 extern "C" int wf_window_attention_fwd_train(const float* x, const float* ln_w,
@@ -1027,9 +1061,12 @@ extern "C" int wf_window_attention_fwd_train(const float* x, const float* ln_w,
                                              float* lse, int64_t B, int64_t C, int64_t D1,
                                              int64_t H1, int64_t W1, int64_t ws, int64_t heads,
                                              float scale, int precision, void* stream) {
-  return window_attention_impl(x, ln_w, ln_b, ln_eps, wqkv_bf16x2, bqkv, bias, 0, wproj_bf16x2,
-                               bproj, out, workspace, lse, B, C, D1, H1, W1, ws, heads, scale,
-                               precision, stream);
+  const int64_t dhw[3] = {D1, H1, W1};
+  return window_attention_call(
+      __func__, dhw, 1, B, C, heads, ws, precision,
+      ATTN_RASTER | (ln_w ? ATTN_LN : 0) | (lse ? ATTN_LSE : 0), ATTN_QKV_RULE,
+      {&x, ln_w, ln_b, ln_eps, wqkv_bf16x2, bqkv, bias, wproj_bf16x2, bproj, out, workspace, lse, scale},
+      stream);
 }
 
 extern "C" int wf_window_attention_fwd_table(const float* x, const float* ln_w,
@@ -1040,11 +1077,12 @@ extern "C" int wf_window_attention_fwd_table(const float* x, const float* ln_w,
                                              int64_t B, int64_t C, int64_t D1, int64_t H1,
                                              int64_t W1, int64_t ws, int64_t heads, float scale,
                                              int precision, void* stream) {
-  WF_REQUIRE(ws == 8 && C == 16 * heads,
-             "table-bias attention is implemented for window 8 and head_dim 16");
-  return window_attention_impl(x, ln_w, ln_b, ln_eps, wqkv_bf16x2, bqkv, table, (int)ws,
-                               wproj_bf16x2, bproj, out, workspace, nullptr, B, C, D1, H1, W1,
-                               ws, heads, scale, precision, stream, ATTN_QKV_RULE);
+  const int64_t dhw[3] = {D1, H1, W1};
+  return window_attention_call(
+      __func__, dhw, 1, B, C, heads, ws, precision, ATTN_RASTER | ATTN_TABLE | (ln_w ? ATTN_LN : 0),
+      ATTN_QKV_RULE,
+      {&x, ln_w, ln_b, ln_eps, wqkv_bf16x2, bqkv, table, wproj_bf16x2, bproj, out, workspace, nullptr, scale},
+      stream);
 }
 
 extern "C" int wf_window_attention_fwd(const float* x, const float* ln_w, const float* ln_b,
@@ -1057,31 +1095,6 @@ extern "C" int wf_window_attention_fwd(const float* x, const float* ln_w, const 
   return wf_window_attention_fwd_train(x, ln_w, ln_b, ln_eps, wqkv_bf16x2, bqkv, bias,
                                        wproj_bf16x2, bproj, out, workspace, nullptr, B, C, D1,
                                        H1, W1, ws, heads, scale, precision, stream);
-}
-
-// ---- all LL levels of one Block in one launch set -----------------------------------------
-// The levels share the weights, the window and head_dim, and do not depend on one another, so
-// they are one problem of sum(rows) logical rows: the qkv GEMM gathers each row from its level
-// (MAP_LEVELS), the core runs over sum(windows), the proj GEMM is the identity-map one.  Every
-// row's arithmetic is what the per-level call does, so the outputs are bitwise equal: a GEMM row
-// does not depend on the rows it shares a launch with, and the core's result depends on its grid
-// only through which of its two loops a window takes, which the merged launch keeps per level.
-// Where the rule says so (attn_qkv_fused: C = 48 and 256 or more (window, head)s) there is no qkv
-// GEMM launch at all: the core computes q / k / v from the level rasters and the weight, bitwise
-// the GEMM's values, and the qkv part of the workspace is left untouched.
-extern "C" int64_t wf_window_attention_levels_workspace_bytes(const int64_t* dhw, int nlev,
-                                                              int64_t B, int64_t C,
-                                                              int precision) {
-  AttnLevels L;
-  if (attn_levels_plan(dhw, nlev, B, C, C / 16, L)) return WF_E_SHAPE;
-  return attn_workspace(L.row0[nlev], C, precision).bytes;
-}
-
-extern "C" int wf_window_attention_levels_fused(const int64_t* dhw, int nlev, int64_t B, int64_t C,
-                                               int64_t heads, int precision) {
-  AttnLevels L;
-  if (!valid_prec(precision) || attn_levels_plan(dhw, nlev, B, C, heads, L)) return 0;
-  return attn_qkv_fused(L.row0[nlev] / (kAttnLevelsWs * kAttnLevelsWs * kAttnLevelsWs), heads, C) ? 1 : 0;
 }
 
 extern "C" int wf_window_attention_fwd_levels(const float* const* x, const int64_t* dhw, int nlev,
@@ -1102,64 +1115,8 @@ extern "C" int wf_window_attention_fwd_levels_mode(const float* const* x, const 
                                                    const float* bproj, float* out, void* workspace,
                                                    int64_t B, int64_t C, int64_t heads, float scale,
                                                    int precision, void* stream, int qkv_mode) {
-  WF_REQUIRE(qkv_mode >= ATTN_QKV_RULE && qkv_mode <= ATTN_QKV_FUSED,
-             "qkv_mode: -1 (the rule), 0 (staged) or 1 (q/k/v in the core)");
-  AttnLevels L;
-  if (const char* why = attn_levels_plan(dhw, nlev, B, C, heads, L))
-    return fail(WF_E_SHAPE, std::string(__func__) + ": " + why);
-  WF_REQUIRE(valid_prec(precision), "unknown precision");
-  WF_REQUIRE_PTR(x);
-  for (int l = 0; l < nlev; ++l) {
-    WF_REQUIRE_PTR(x[l]);
-    WF_REQUIRE(reinterpret_cast<uintptr_t>(x[l]) % 16 == 0, "level sources must be 16-byte aligned");
-  }
-  WF_REQUIRE_PTR(wqkv_bf16x2);
-  WF_REQUIRE_PTR(table);
-  WF_REQUIRE_PTR(wproj_bf16x2);
-  WF_REQUIRE_PTR(out);
-  WF_REQUIRE_PTR(workspace);
-  constexpr int64_t ws = kAttnLevelsWs, N = ws * ws * ws;
-  const int64_t rows = L.row0[nlev];
-  hipStream_t s = (hipStream_t)stream;
-  void* qkv = workspace;
-  void* ao = reinterpret_cast<char*>(workspace) + attn_workspace(rows, C, precision).ao;
-  const int fused = pick_qkv_fused(qkv_mode, rows / N, heads, C);
-  if (fused < 0) return WF_E_SHAPE;
-  // 1. qkv = Linear(window_partition(x_l)) of every level: the rows' sources come from lv_*.
-  //    A launch of its own (staged), or the argument block the core computes q / k / v from
-  GemmArgs g = qkv_gemm_args(x[0], nullptr, nullptr, 0.f, wqkv_bf16x2, bqkv, qkv, rows, B, C, 0,
-                             0, 0, ws, precision);
-  set_level_sources(g, x, L);
-  // the core loop each level's own launch takes (attn_tbl_kernel, pair_end): the merged launch
-  // keeps it per level, so the levels on the query-pair loop must come first
-  int64_t pair_windows = 0;
-  bool prefix = true;
-  for (int l = 0; l < nlev; ++l) {
-    const int64_t wl = (L.row0[l + 1] - L.row0[l]) / N;
-    if (attn_tbl_pair_loop(wl * heads)) {
-      prefix = prefix && pair_windows == L.row0[l] / N;
-      pair_windows = L.row0[l + 1] / N;
-    }
-  }
-  if (!prefix || (!fused && !try_launch_gemm_rows(g, s, true) && !try_launch_gemm_kc(g, s))) {
-    // no multi-level instantiation takes this width (or a coarse level before a finer one):
-    // one call per level, into the same output
-    for (int l = 0; l < nlev; ++l) {
-      const int rc = window_attention_impl(x[l], nullptr, nullptr, 0.f, wqkv_bf16x2, bqkv, table,
-                                           (int)ws, wproj_bf16x2, bproj, out + L.row0[l] * C,
-                                           workspace, nullptr, B, C, L.D[l], L.H[l], L.W[l], ws,
-                                           heads, scale, precision, stream, qkv_mode);
-      if (rc) return rc;
-    }
-    return WF_OK;
-  }
-  int rc = fused ? WF_OK : check_launch("wf_window_attention_fwd_levels(qkv)");
-  if (rc) return rc;
-  // 2. softmax(q k^T * scale + bias) v over all levels' windows
-  rc = launch_attn_core(qkv, table, ao, nullptr, rows / N, (int)N, (int)heads, 16, scale,
-                        precision, s, (int)ws, pair_windows, fused ? &g : nullptr);
-  if (rc) return rc;
-  // 3. proj; window-major rows, level after level
-  return launch_gemm(proj_gemm_args(ao, wproj_bf16x2, bproj, out, rows, C, precision), s,
-                     "wf_window_attention_fwd_levels(proj)");
+  return window_attention_call(
+      __func__, dhw, nlev, B, C, heads, kAttnLevelsWs, precision, ATTN_TABLE, qkv_mode,
+      {x, nullptr, nullptr, 0.f, wqkv_bf16x2, bqkv, table, wproj_bf16x2, bproj, out, workspace, nullptr, scale},
+      stream);
 }

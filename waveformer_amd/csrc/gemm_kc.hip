@@ -440,16 +440,19 @@ int gemm_kc_pick_nt(const GemmArgs& g) {
       nt = c;
     if (blocks(nt) >= 512) break;
   }
+  // MAP_LEVELS serves K = 96 / N = 288 alone (gemm_levels_callsite), with the chunk widths that
+  // shape picks (3 for small M, else 6).  The width is asked here: a wider K at a small M picks
+  // 6 as well and used to be taken, against what gemm_levels_callsite and DESIGN.md 6.18 say
+  if (g.a_map == MAP_LEVELS && (g.K != 96 || g.N != 288 || (nt != 6 && nt != 3))) return 0;
   return nt;
 }
 
 int try_launch_gemm_kc(const GemmArgs& g, hipStream_t s) {
   const int nt = gemm_kc_pick_nt(g);
   if (nt == 0) return 0;
-  if (g.a_map == MAP_LEVELS) {  // the chunk widths K = 96 / N = 288 picks (3 for small M, else 6)
+  if (g.a_map == MAP_LEVELS) {
     if (nt == 6) go_kc<6, MAP_LEVELS, EPI_STORE>(g, s);
-    else if (nt == 3) go_kc<3, MAP_LEVELS, EPI_STORE>(g, s);
-    else return 0;
+    else go_kc<3, MAP_LEVELS, EPI_STORE>(g, s);
   } else if (g.a_map == MAP_WINDOW) dispatch_kc<MAP_WINDOW, EPI_STORE>(nt, g, s);
   else if (g.a_map == MAP_MERGE) dispatch_kc<MAP_MERGE, EPI_STORE>(nt, g, s);
   else if (g.epi == EPI_LN_GELU) dispatch_kc<MAP_IDENTITY, EPI_LN_GELU>(nt, g, s);

@@ -408,16 +408,18 @@ static void dispatch_nt(int nt, const GemmArgs& g, dim3 grid, size_t lds, hipStr
   }
 }
 
-int try_launch_gemm_rows(const GemmArgs& g, hipStream_t s, bool single_chunk_only) {
-  if (g.N % 16 != 0 || g.K < 8 || g.M >= ((int64_t)1 << 31)) return 0;
-  if (g.a_map == MAP_LEVELS ? !gemm_levels_callsite(g) : !gemm_known_callsite(g)) return 0;
+// what try_launch_gemm_rows launches for g (false: it does not take the shape): everything it
+// decides before the launch, so a caller can ask without launching
+bool gemm_rows_pick(const GemmArgs& g, bool single_chunk_only, GemmRowsPick& r) {
+  if (g.N % 16 != 0 || g.K < 8 || g.M >= ((int64_t)1 << 31)) return false;
+  if (g.a_map == MAP_LEVELS ? !gemm_levels_callsite(g) : !gemm_known_callsite(g)) return false;
   // the LN+GELU instantiations are specialised to the CCF_FFN pwconv's loader and storage
   const int64_t out_bytes = g.M * g.ldo * ((g.prec == PREC_BF16 || g.a_bf16) ? 2 : 4);
   if (g.epi == EPI_LN_GELU && (g.K > 64 || out_bytes >= ((int64_t)1 << 31) || (g.a_ln != LN_GIVEN && g.a_ln != LN_NONE) || g.a_gelu ||
                                (g.out_bf16 != 0) != (g.prec == PREC_BF16 || g.a_bf16 != 0)))
-    return 0;
+    return false;
   if (g.epi == EPI_SUBVOXEL && (g.out_bf16 || (g.N / 8) % 4 != 0 || g.a_map != MAP_IDENTITY))
-    return 0;
+    return false;
   const bool split = g.prec == PREC_SPLIT;
   const int K32 = (g.K + 31) & ~31;
   const size_t per_col = (size_t)(split ? 2 : 1) * (K32 + WF_LDS_KPAD) * 2;
@@ -435,21 +437,30 @@ int try_launch_gemm_rows(const GemmArgs& g, hipStream_t s, bool single_chunk_onl
       break;
     }
   }
-  if (nt == 0) return 0;
+  if (nt == 0) return false;
   size_t lds = (size_t)nt * 16 * per_col + (size_t)(2 * K32 + 3 * nt * 16) * 4;
   if (g.epi == EPI_LN_GELU && g.prec != PREC_BF16 && !g.a_bf16)  // output staging per wave
     lds += (size_t)(rows_w12(g) ? 12 * 8 : 8 * 16) * (nt * 16 + 4) * 4;
-  if (lds > 160 * 1024) return 0;
+  if (lds > 160 * 1024) return false;
   const int chunks = tiles / nt;
-  if (single_chunk_only && chunks > 1) return 0;
-  if (g.a_map == MAP_LEVELS && nt != 9) return 0;  // the one instantiation (K = 48 / N = 144)
+  if (single_chunk_only && chunks > 1) return false;
+  if (g.a_map == MAP_LEVELS && nt != 9) return false;  // the one instantiation (K = 48 / N = 144)
   const int64_t ntiles = (g.M + 15) / 16;
   int64_t gx = cdiv(ntiles, 8);
   // ~2 workgroups of 8 waves per CU; one per CU when the weight chunk fills the LDS
   const int64_t cap = lds > 80 * 1024 ? 256 : (512 + chunks - 1) / chunks;
   if (gx > cap) gx = cap;
   if (gx < 1) gx = 1;
-  dim3 grid((unsigned)gx, (unsigned)chunks);
+  r = {nt, lds, (unsigned)gx, (unsigned)chunks};
+  return true;
+}
+
+int try_launch_gemm_rows(const GemmArgs& g, hipStream_t s, bool single_chunk_only) {
+  GemmRowsPick r;
+  if (!gemm_rows_pick(g, single_chunk_only, r)) return 0;
+  const int nt = r.nt;
+  const size_t lds = r.lds;
+  const dim3 grid(r.gx, r.chunks);
   if (g.a_map == MAP_LEVELS) go_rows<9, MAP_LEVELS, EPI_STORE>(g, grid, lds, s);
   else if (g.a_map == MAP_WINDOW) dispatch_nt<MAP_WINDOW, EPI_STORE>(nt, g, grid, lds, s);
   else if (g.a_map == MAP_MERGE) dispatch_nt<MAP_MERGE, EPI_STORE>(nt, g, grid, lds, s);

@@ -180,20 +180,14 @@ int launch_instnorm_partial(const float* x, int64_t ldx, int64_t B, int64_t C, i
                             double* acc, hipStream_t s);
 // streaming variant (gemm_rows.hip); returns 1 if it took the shape, 0 to fall back
 int try_launch_gemm_rows(const GemmArgs& g, hipStream_t s, bool single_chunk_only);
-
-// ---- windowed attention core over a (B_, N, 3C) qkv buffer (bf16, or fp32 when SPLIT) ----
-// table_ws != 0: `bias` is the (T, heads) relative_position_bias_table and the index is the
-// reference's formula for window table_ws (8 with head_dim 16 implemented; inference only: a
-// non-null lse is refused)
-// pair_windows (table bias, inference): windows [0, pair_windows) may take the core's
-// query-pair loop, the rest its one-sub-tile loop (< 0: all may); attn_tbl_pair_loop(wh) is the
-// loop a launch of wh (window, head)s takes on its own
-// fused (table bias, inference): the qkv GEMM's argument block (MAP_LEVELS rows); the core then
-// computes q / k / v itself from x and the weight and `qkv` is not read (attn_tbl_kernel_fused)
-int launch_attn_core(const void* qkv, const float* bias, void* out, float* lse, int64_t Bw,
-                     int N, int heads, int hd, float scale, int prec, hipStream_t s,
-                     int table_ws = 0, int64_t pair_windows = -1, const GemmArgs* fused = nullptr);
-bool attn_tbl_pair_loop(int64_t wh);
+// what it would launch (column tiles per workgroup, LDS bytes, grid), without launching; false
+// where it returns 0
+struct GemmRowsPick {
+  int nt;
+  size_t lds;
+  unsigned gx, chunks;
+};
+bool gemm_rows_pick(const GemmArgs& g, bool single_chunk_only, GemmRowsPick& r);
 
 // ---- depthwise 3^3 conv + bias + LayerNorm + GELU over a channel-last volume ------------
 // (bf16 storage for PREC_BF16, fp32 for PREC_SPLIT)

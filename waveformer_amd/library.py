@@ -52,7 +52,9 @@ def _round256(n):
 
 def attn_workspace_bytes(B, C, D1, H1, W1):
     """wf_window_attention_workspace_bytes(..., WF_PREC_BF16X3) in plain (Sym)int arithmetic
-    (fake tensors and dynamic shapes cannot call into the library): qkv + core output, fp32."""
+    (fake tensors and dynamic shapes cannot call into the library): qkv + core output, fp32.
+    The only restatement of attn_workspace (csrc/attn_plan.hpp) in Python; real calls ask the
+    library, and tests/test_library.py compares the two."""
     rows = B * D1 * H1 * W1
     return _round256(rows * 3 * C * 4) + _round256(rows * C * 4)
 

@@ -1485,32 +1485,37 @@ def window_attention(x_cl: torch.Tensor, wqkv: torch.Tensor, bqkv: Optional[torc
         out = _window_attention_levels((x_cl, *more), wqkv, bqkv, bias, wproj, bproj, ws, heads,
                                        scale, ln, prec, qkv_mode)
         return out if more else out[0]
-    wq = split_weight(wqkv, prec=prec)
-    wp = split_weight(wproj, prec=prec)
-    if bqkv is not None:
-        _check(bqkv, "qkv.bias")
-    if bproj is not None:
-        _check(bproj, "proj.bias")
-    _check(bias, "bias")
     N = ws ** 3
     table = tuple(bias.shape) == ((2 * ws - 1) ** 3, heads)
     if not table and tuple(bias.shape) != (heads, N, N):
         raise ValueError(f"window_attention: bias {tuple(bias.shape)} is neither ({heads},{N},{N}) "
                          f"nor the ({(2 * ws - 1) ** 3},{heads}) table")
+    wq, wp, work = _attention_operands((x_cl,), wqkv, bqkv, bias, wproj, bproj, prec)
     lw = lb = None
     eps = 0.0
     if ln is not None:
         lw, lb, eps = ln
     out = torch.empty_like(x_cl)
-    prec = _prec() if prec is None else prec
-    wsb = _lib.query("wf_window_attention_workspace_bytes", B, C, D1, H1, W1, prec)
-    work = torch.empty(wsb, dtype=torch.uint8, device=x_cl.device)
     _lib.call("wf_window_attention_fwd_table" if table else "wf_window_attention_fwd",
               x_cl.data_ptr(), _ptr(lw), _ptr(lb), float(eps),
               wq.data_ptr(), _ptr(bqkv), bias.data_ptr(), wp.data_ptr(), _ptr(bproj),
               out.data_ptr(), work.data_ptr(), B, C, D1, H1, W1, ws, heads, float(scale),
               prec, _stream())
     return out
+
+
+def _attention_operands(levels, wqkv, bqkv, bias, wproj, bproj, prec):
+    """What every window attention call does first: check the small tensors, split the two
+    weights, and allocate the workspace -- the sum of wf_window_attention_workspace_bytes over the
+    rasters, which is the level list's own size (csrc/attn_plan.hpp attn_workspace).  Returns
+    (wqkv split, wproj split, workspace)."""
+    for t, name in ((bqkv, "qkv.bias"), (bproj, "proj.bias"), (bias, "bias")):
+        if t is not None:
+            _check(t, name)
+    wsb = sum(_lib.query("wf_window_attention_workspace_bytes", x.shape[0], x.shape[4],
+                         *x.shape[1:4], prec) for x in levels)
+    work = torch.empty(wsb, dtype=torch.uint8, device=levels[0].device)
+    return split_weight(wqkv, prec=prec), split_weight(wproj, prec=prec), work
 
 
 def _window_attention_levels(levels, wqkv, bqkv, bias, wproj, bproj, ws, heads, scale, ln, prec,
@@ -1526,16 +1531,10 @@ def _window_attention_levels(levels, wqkv, bqkv, bias, wproj, bproj, ws, heads, 
         if x.dim() != 5 or x.shape[0] != B or x.shape[4] != C:
             raise ValueError("window_attention(more=...): level batch/channels mismatch")
         dhw.extend(x.shape[1:4])
-    for t, name in ((bqkv, "qkv.bias"), (bproj, "proj.bias"), (bias, "bias")):
-        if t is not None:
-            _check(t, name)
-    wq = split_weight(wqkv, prec=prec)
-    wp = split_weight(wproj, prec=prec)
+    wq, wp, work = _attention_operands(levels, wqkv, bqkv, bias, wproj, bproj, prec)
     darr = (ctypes.c_int64 * len(dhw))(*dhw)
-    wsb = _lib.query("wf_window_attention_levels_workspace_bytes", darr, len(levels), B, C, prec)
     rows = [x.numel() // C for x in levels]
     out = torch.empty((sum(rows), C), dtype=torch.float32, device=levels[0].device)
-    work = torch.empty(max(wsb, 0), dtype=torch.uint8, device=out.device)
     arr = (ctypes.c_void_p * len(levels))(*[x.data_ptr() for x in levels])
     _lib.call("wf_window_attention_fwd_levels_mode", arr, darr, len(levels), wq.data_ptr(),
               _ptr(bqkv), bias.data_ptr(), wp.data_ptr(), _ptr(bproj), out.data_ptr(),
