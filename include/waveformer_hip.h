@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define WF_ABI_VERSION 28
+#define WF_ABI_VERSION 29
 
 enum { WF_PREC_BF16 = 0, WF_PREC_BF16X3 = 1, WF_PREC_FP16 = 2 };
 
@@ -1028,6 +1028,35 @@ int wf_spline_zoom_axis_plan(int64_t n, int64_t on, int64_t seg, int64_t* plan);
  * the largest label whose sum is >= 0.5 wins, else 0.  One pass, no per-label volumes.      */
 int wf_zoom_seg_linear(const int16_t* seg, int64_t D, int64_t H, int64_t W, int64_t oD,
                        int64_t oH, int64_t oW, int16_t* out, void* stream);
+
+/* ======================================================================================
+ * Training batches (ABI 29): the crop + pad of light_training/dataloading/base_data_loader.py
+ * (DataLoaderMultiProcess.generate_train_batch) for a whole batch of cases that already lie on
+ * the device.  Plain loads and vector stores, no atomics, no workspace: bitwise repeatable.
+ * ====================================================================================== */
+
+enum { WF_SEG_INT8 = 0, WF_SEG_INT16 = 1, WF_SEG_FP32 = 2 };
+
+/* out_data (B, C, pz, py, px) and out_seg (B, S, pz, py, px) fp32: sample b is the box
+ * [lb, lb + patch) of case b, the part of the box outside the case zero in both outputs (the
+ * reference pads its segmentation with 0 as well).  records: a HOST table of B rows of 8 int64
+ * {data pointer, seg pointer, D, H, W, lb_z, lb_y, lb_x}: data (C, D, H, W) fp32 and seg
+ * (S, D, H, W) of seg_kind (WF_SEG_*; converted to fp32, an int8 -1 becomes -1.0f), both device
+ * pointers.  The table is read during the call and handed to the kernel by value, 16 rows per
+ * launch: no device table, no copy, no synchronisation, capturable.  A box may hang over any
+ * edge or lie wholly outside its case (all zeros).  Every output element is written.  16-byte
+ * loads where lb_x, W, px and D*H*W are multiples of 4 and the case's base is aligned to 4
+ * elements; dword (element) loads otherwise.  Needs D*H*W and pz*py*px below 2^31 and
+ * C + S <= 4095.                                                                              */
+int wf_crop_pad_batch(const int64_t* records, int64_t B, int64_t C, int64_t S, int seg_kind,
+                      int64_t pz, int64_t py, int64_t px, float* out_data, float* out_seg,
+                      void* stream);
+
+/* Host only: one axis of the above.  plan (3 host int64) = {dst0, src0, n} such that
+ * out[dst0 : dst0 + n] = in[src0 : src0 + n] and the rest of out[0 : patch] is zero; {0, 0, 0}
+ * when the box misses the case.  Any lb; 1 <= patch, extent < 2^31.  Computed by the code the
+ * launch path runs (csrc/loader_plan.hpp).                                                    */
+int wf_crop_pad_axis_plan(int64_t lb, int64_t patch, int64_t extent, int64_t* plan);
 
 #ifdef __cplusplus
 }

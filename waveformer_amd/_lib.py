@@ -177,9 +177,12 @@ SIGNATURES = {
     "wf_spline_zoom_axis": (_I, [_P, _P, _I64, _I64, _I64, _I64, _I, _I64, _P, _P]),
     "wf_spline_zoom_axis_plan": (_I, [_I64, _I64, _I64, _P]),
     "wf_zoom_seg_linear": (_I, [_P] + [_I64] * 6 + [_P, _P]),
+    # training batches (crop + pad of resident cases)
+    "wf_crop_pad_batch": (_I, [_P, _I64, _I64, _I64, _I] + [_I64] * 3 + [_P, _P, _P]),
+    "wf_crop_pad_axis_plan": (_I, [_I64, _I64, _I64, _P]),
 }
 
-ABI_VERSION = 28
+ABI_VERSION = 29
 _lock = threading.Lock()
 _lib = None
 _err = None

@@ -2392,3 +2392,74 @@ def zoom_seg_linear(seg: torch.Tensor, size: Sequence[int]) -> torch.Tensor:
     _lib.call("wf_zoom_seg_linear", seg.data_ptr(), *(int(v) for v in seg.shape), *size,
               out.data_ptr(), _stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------
+# training batches: crop + pad of cases that lie on the device (waveformer_amd.dataloading)
+# ------------------------------------------------------------------------------------------
+SEG_KINDS = {torch.int8: 0, torch.int16: 1, torch.float32: 2}  # WF_SEG_*
+
+
+def crop_pad_axis_plan(lb: int, patch: int, extent: int) -> Tuple[int, int, int]:
+    """(dst0, src0, n) of one axis of a patch box [lb, lb + patch) over a case of `extent`
+    voxels: out[dst0:dst0 + n] = in[src0:src0 + n], the rest of the patch zero
+    (wf_crop_pad_axis_plan, the arithmetic wf_crop_pad_batch launches with).  Needs no GPU."""
+    buf = (ctypes.c_int64 * 3)()
+    _lib.call("wf_crop_pad_axis_plan", int(lb), int(patch), int(extent), buf)
+    return int(buf[0]), int(buf[1]), int(buf[2])
+
+
+def crop_pad_batch(cases: Sequence[Tuple[torch.Tensor, torch.Tensor]],
+                   bbox_lbs: Sequence[Sequence[int]], patch: Sequence[int],
+                   out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+                   ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The slice + zero pad of a training batch in one launch (wf_crop_pad_batch).  cases: B
+    pairs (data (C, D, H, W) fp32, seg (S, D, H, W) int8 / int16 / fp32, one dtype for the
+    batch) on one device, of any shapes; bbox_lbs: B lower corners (z, y, x), which may be
+    negative or beyond the case.  Returns (data (B, C, *patch) fp32, seg (B, S, *patch) fp32):
+    sample b is case b's box [lb, lb + patch) with zeros outside the case.  out: the two
+    tensors to write instead of new ones."""
+    patch = _size3(patch, "crop_pad_batch")
+    B = len(cases)
+    if B < 1:
+        raise ValueError("crop_pad_batch: an empty batch")
+    lbs = [tuple(int(v) for v in lb) for lb in bbox_lbs]
+    if len(lbs) != B or any(len(lb) != 3 for lb in lbs):
+        raise ValueError(f"crop_pad_batch: need {B} lower corners (z, y, x), got {bbox_lbs!r}")
+    data0, seg0 = cases[0]
+    if not isinstance(seg0, torch.Tensor) or seg0.dtype not in SEG_KINDS:
+        raise TypeError("crop_pad_batch: seg must be an int8, int16 or float32 tensor, got "
+                        f"{getattr(seg0, 'dtype', type(seg0))}")
+    keep, table = [], (ctypes.c_int64 * (8 * B))()
+    for b, (data, seg) in enumerate(cases):
+        _check(data, "data", contiguous=False)
+        if data.dim() != 4:
+            raise ValueError(f"crop_pad_batch: case {b}: expected data (C, D, H, W), got "
+                             f"{tuple(data.shape)}")
+        C, D, H, W = (int(v) for v in data.shape)
+        _check(seg, "seg", dtype=seg0.dtype, contiguous=False)
+        if data.device != data0.device or seg.device != data0.device:
+            raise RuntimeError(f"crop_pad_batch: case {b} is on {data.device} / {seg.device}, "
+                               f"the batch on {data0.device}")
+        if seg.dim() != 4 or tuple(seg.shape[1:]) != (D, H, W):
+            raise ValueError(f"crop_pad_batch: case {b}: seg {tuple(seg.shape)} does not match "
+                             f"data {tuple(data.shape)}")
+        if C != data0.shape[0] or seg.shape[0] != seg0.shape[0]:
+            raise ValueError(f"crop_pad_batch: case {b} has {C} + {seg.shape[0]} channels, the "
+                             f"first case {data0.shape[0]} + {seg0.shape[0]}")
+        data, seg = data.contiguous(), seg.contiguous()
+        keep += [data, seg]  # a copy made here lives until the launch is enqueued
+        table[8 * b:8 * b + 8] = [data.data_ptr(), seg.data_ptr(), D, H, W, *lbs[b]]
+    C, S = int(data0.shape[0]), int(seg0.shape[0])
+    shapes = ((B, C) + patch, (B, S) + patch)
+    if out is None:
+        out = tuple(torch.empty(s, dtype=torch.float32, device=data0.device) for s in shapes)
+    else:
+        for t, s, name in zip(out, shapes, ("out data", "out seg")):
+            _check(t, name)
+            if tuple(t.shape) != s or t.device != data0.device:
+                raise ValueError(f"crop_pad_batch: {name} {tuple(t.shape)} on {t.device}, "
+                                 f"expected {s} on {data0.device}")
+    _lib.call("wf_crop_pad_batch", table, B, C, S, SEG_KINDS[seg0.dtype], *patch,
+              out[0].data_ptr(), out[1].data_ptr(), _stream())
+    return out[0], out[1]
